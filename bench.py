@@ -7,7 +7,7 @@ synthetic samples, one step() per timed step (one kernel launch), FMA float
 contract.  With --gpus N (launched by torch.distributed.run) every rank owns
 the same work as N = 1 -- one 2^28-sample channel of its own -- so the N = 1,
 2, 4, 8 values form one weak-scaling series (no collective in the timed
-region).  Beside it, in the same line at N > 1 (at N = 1 with --share),
+region).  Beside it, in the same line with --full at N > 1 (at N = 1 with --full --share),
 `configs2_share` measures configs[2]'s layout: 8 channels of 2^28 per GPU (64
 over 8 GPUs), one batched step per rank (weak scaling too), and the RCCL
 gather of every channel's decimated output to rank 0 (32 GiB at N = 8), timed
@@ -19,9 +19,17 @@ decimator, fused), corr (config 5, 1024-lag correlator), fir (config 1 shape on
 the GPU), up (interpolator), fifo / iq (host -> HBM ring or capture replay
 feeding config 4's chain; bound by the host link).
 
-Reported beside the GPU number:
-  roofline      dominant kernel's algorithmic bytes / its HIP-event time, vs 8 TB/s
-  cpu_baseline  the REFERENCE (oracle/_ref, g++ -O2) timed on this host, 1 thread
+A plain run (no --full) sets up, warms up, times the steps and prints the line:
+`value`, `ms_per_step` and the roofline figures derived from the timed steps'
+own HIP events.  --dump-outputs DIR also writes what the last timed step
+computed (dump_outputs()).
+
+With --full, beside the GPU number (each leg has its own --no-... switch):
+  parity        sha256 of every decimated channel against tests/golden/channel_digests.json
+  configs2_share  configs[2]'s per-GPU share and its gather (N > 1; N = 1 with --share too)
+  cpu_baseline  the REFERENCE (oracle/_ref, g++ -O2) timed on this host, 1 thread,
+                on all cores, and the -O0 build
+  pcie_inclusive  the host-vector step (H2D, kernel, D2H)
 """
 from __future__ import annotations
 
@@ -68,7 +76,7 @@ def parse(argv=None):
     p.add_argument("--channels-per-gpu", type=int, default=None)
     p.add_argument("--no-share", action="store_true", help="skip the configs[2] per-GPU share measurement (N > 1)")
     p.add_argument("--share", action="store_true",
-                   help="measure the configs[2] per-GPU share at N = 1 too (default: N > 1 only, so the N = 1 "
+                   help="with --full: measure the configs[2] per-GPU share at N = 1 too (default: N > 1 only, so the N = 1 "
                         "command's kernel trace holds the headline's launches alone)")
     p.add_argument("--fp", default="fma", choices=["fma", "strict"])
     p.add_argument("--no-cpu-baseline", action="store_true")
@@ -83,7 +91,17 @@ def parse(argv=None):
     p.add_argument("--no-parity", action="store_true",
                    help="skip the post-timing digest check of the decimated channels")
     p.add_argument("--digests", default=os.path.join(ROOT, "tests", "golden", "channel_digests.json"))
-    return p.parse_args(argv)
+    p.add_argument("--full", action="store_true",
+                   help="also run the legs beside the headline figure: parity digests, the configs[2] share "
+                        "(N > 1), the CPU baselines and the PCIe-inclusive step (each has its --no-... switch)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write the last timed step's outputs as DIR/<name>.npy "
+                        "(see dump_outputs())")
+    args = p.parse_args(argv)
+    if not args.full:
+        # a plain run does only what `value` and `ms_per_step` need
+        args.no_cpu_baseline = args.no_pcie = args.no_parity = args.no_share = True
+    return args
 
 
 def _free_port() -> int:
@@ -312,6 +330,10 @@ class Workload:
     def step(self):
         raise NotImplementedError
 
+    def outputs(self) -> dict:
+        """What a caller of step() receives from the last step, by name."""
+        return {"y": self.y}
+
 
 class DecimWorkload(Workload):
     dtype = "f32"
@@ -400,6 +422,9 @@ class CorrWorkload(Workload):
         found = first != self.D.NO_DETECTION
         self.last = (found, first if found else -1)
 
+    def outputs(self):
+        return {"detection": np.array([float(self.last[0]), float(self.last[1])])}
+
 
 class FirWorkload(Workload):
     dtype = "f32"
@@ -408,7 +433,9 @@ class FirWorkload(Workload):
 
     def __init__(self, S, torch, L, channels, rank, fp):
         from srcdsp_amd.design import hamming_sinc
-        self.x = torch.randint(-2048, 2048, (L,), device=DEV.name).float()
+        g = torch.Generator(device=DEV.name)
+        g.manual_seed(SEED)  # the same input in every run
+        self.x = torch.randint(-2048, 2048, (L,), device=DEV.name, generator=g).float()
         self.y = torch.empty(L, dtype=torch.complex64, device=DEV.name)
         self.f = S.FilterFir(hamming_sinc(31, 0.2), "float", "complex<float>", "float", "float", fp=fp)
         self.name = "fir_f32_t31"
@@ -1039,6 +1066,48 @@ def measure_share(S, torch, args, world, rank, L, slay, table=None) -> dict:
     return out
 
 
+# ---------------------------------------------------------------- outputs
+DUMP_BUDGET_BYTES = 48 << 20  # all files of all ranks together (the limit on a dump is 64 MB)
+
+
+def dump_outputs(work, out_dir, rank, world, torch) -> dict:
+    """--dump-outputs: write what the last timed step left in the workload's
+    outputs() as <out_dir>/<name>.npy (<name>_rank<r>.npy at N > 1), so two
+    builds run with the same arguments can be compared output for output (the
+    inputs are seeded: identical from run to run).
+
+    Complex values become (re, im) pairs, and every array is saved as rows of
+    its last axis: float32 for complex64 / float32 / int16 outputs (exact),
+    float64 otherwise.  DUMP_BUDGET_BYTES is divided evenly over the ranks and
+    each rank's outputs; an output larger than its share is sampled: k rows,
+    the i-th drawn by numpy's default_rng(SEED) from the i-th of k strata
+    [i*n // k, (i+1)*n // k) that tile all n rows, so the choice is the same in
+    every run of the same shape and reaches the last rows as well as the
+    first.  Returns what was written, for the line."""
+    os.makedirs(out_dir, exist_ok=True)
+    outs = work.outputs()
+    per = DUMP_BUDGET_BYTES // (world * max(1, len(outs)))
+    written = {}
+    for name, v in outs.items():
+        t = torch.as_tensor(v)
+        if t.is_complex():
+            t = torch.view_as_real(t)
+        rows = t.reshape(-1, t.shape[-1] if t.dim() > 1 else 1)
+        exact32 = rows.dtype in (torch.float32, torch.int16, torch.int8, torch.uint8)
+        dt = torch.float32 if exact32 else torch.float64
+        n = rows.shape[0]
+        k = max(1, per // (rows.shape[1] * (4 if exact32 else 8)))
+        if n > k:
+            lo = np.arange(k + 1, dtype=np.int64) * n // k  # stratum bounds: lo[0] = 0, lo[k] = n
+            idx = lo[:-1] + np.random.default_rng(SEED).integers(0, np.diff(lo))
+            rows = rows.index_select(0, torch.from_numpy(idx).to(rows.device))
+        a = rows.to(dt).cpu().numpy()
+        fname = f"{name}.npy" if world == 1 else f"{name}_rank{rank}.npy"
+        np.save(os.path.join(out_dir, fname), a)
+        written[fname] = {"rows": int(a.shape[0]), "of": int(n), "dtype": str(a.dtype)}
+    return written
+
+
 # ---------------------------------------------------------------- main
 def main(argv=None, S=None, dev=None):
     """argv: the command line (default sys.argv); S: the operator package
@@ -1075,6 +1144,9 @@ def main(argv=None, S=None, dev=None):
     work_name, work_dtype = work.name, work.dtype
     wall, kern_ms = timed_steps(work, args, world, torch)
     kern_avg_ms = float(np.mean(kern_ms))
+    dumped = None
+    if args.dump_outputs:  # before the parity leg steps the filters again
+        dumped = dump_outputs(work, args.dump_outputs, rank, world, torch)
     table = parity = None
     if args.workload == "decim" and not args.no_parity:  # outside the timed region
         table = _load_digests(args.digests)
@@ -1201,6 +1273,8 @@ def main(argv=None, S=None, dev=None):
                                            "resident channel(s) once, and compares sha256 of each channel's output "
                                            "with the oracle/reference digest of that channel id; counts summed "
                                            "over ranks"))
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
         if share is not None:
             line["configs2_share"] = share
         if args.workload == "corr":

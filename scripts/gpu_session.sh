@@ -6,7 +6,8 @@
 #
 #   smoke            __graft_entry__.py smoke
 #   tests            pytest -m gpu (PYTEST_K: -k filter)
-#   bench            bench.py ${BENCH_ARGS} (default: the headline, driver protocol --steps 20 --warmup 5)
+#   bench            bench.py --full ${BENCH_ARGS} (default: the headline with every leg beside it, --steps 20
+#                    --warmup 5 in a fresh process)
 #   bench_all        every workload's bench line (steady protocol)
 #   bench_cold       every workload's line under the driver's protocol (--warmup 5 --steps 20), IDLE s apart
 #   bench8           config 3's per-GPU share (--channels-per-gpu 8), driver protocol and steady
@@ -56,21 +57,21 @@ for s in ${STEPS:-smoke tests bench}; do
     smoke) step smoke_$TAG 300 python -u __graft_entry__.py smoke ;;
     tests) step tests_$TAG 1000 python -u -m pytest tests -m gpu -q --timeout 120 --timeout-method thread \
              --maxfail=30 --durations=25 ${PYTEST_K:+-k "$PYTEST_K"} ;;
-    bench) step bench_$TAG 300 python -u bench.py ${BENCH_ARGS:---steps 20 --warmup 5} ;;
+    bench) step bench_$TAG 300 python -u bench.py --full ${BENCH_ARGS:---steps 20 --warmup 5} ;;
     bench_all)
       for w in decim mixdecim ci16decim corr fir up; do
-        step bench_${w}_$TAG 300 python -u bench.py --workload $w --no-cpu-baseline --no-pcie
+        step bench_${w}_$TAG 300 python -u bench.py --full --workload $w --no-cpu-baseline --no-pcie
       done ;;
     bench8)  # config 3's per-GPU share (8 x 2^28 channels per step): driver protocol, then steady
-      step bench8cold_$TAG 300 python -u bench.py --channels-per-gpu 8 --warmup 5 --steps 20 --no-cpu-baseline --no-pcie
-      step bench8_$TAG 300 python -u bench.py --channels-per-gpu 8 --warmup 20 --steps 50 --no-cpu-baseline --no-pcie ;;
+      step bench8cold_$TAG 300 python -u bench.py --full --channels-per-gpu 8 --warmup 5 --steps 20 --no-cpu-baseline --no-pcie
+      step bench8_$TAG 300 python -u bench.py --full --channels-per-gpu 8 --warmup 20 --steps 50 --no-cpu-baseline --no-pcie ;;
     bench_cold)  # the driver's protocol for every workload, each a fresh process after ${IDLE:-8} s idle
       for w in decim mixdecim ci16decim corr fir up; do
         sleep ${IDLE:-8}
-        step benchcold_${w}_$TAG 300 python -u bench.py --workload $w --no-cpu-baseline --no-pcie --warmup 5 --steps 20
+        step benchcold_${w}_$TAG 300 python -u bench.py --full --workload $w --no-cpu-baseline --no-pcie --warmup 5 --steps 20
       done ;;
     prof) step prof_$TAG 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_$TAG -o run --output-format csv \
-            -- python3 bench.py --no-cpu-baseline --no-pcie ${BENCH_ARGS:---steps 20 --warmup 5} ;;
+            -- python3 bench.py --full --no-cpu-baseline --no-pcie ${BENCH_ARGS:---steps 20 --warmup 5} ;;
     pmc)
       for w in ${PMC_WORKLOADS:-decim}; do
         if [ "$w" = decimx8 ]; then
@@ -126,19 +127,19 @@ for s in ${STEPS:-smoke tests bench}; do
         tests/test_gpu_parity.py -m gpu -q --timeout 120 --timeout-method thread -k "config5 or time_split"
       for rep in 1 2; do
         sleep ${IDLE:-8}
-        step corrlib_benchprod${rep}_$TAG 300 python -u bench.py --workload corr --no-cpu-baseline --no-pcie --warmup 5 --steps 20
+        step corrlib_benchprod${rep}_$TAG 300 python -u bench.py --workload corr --warmup 5 --steps 20
         sleep ${IDLE:-8}
-        SRCDSP_HIP_LIB=$L step corrlib_bench${rep}_$TAG 300 python -u bench.py --workload corr --no-cpu-baseline --no-pcie \
+        SRCDSP_HIP_LIB=$L step corrlib_bench${rep}_$TAG 300 python -u bench.py --workload corr \
           --warmup 5 --steps 20
         sleep ${IDLE:-8}
         SRCDSP_HIP_LIB=$L SRCDSP_CORR_MFMA_PL=2 step corrlib_bench2l${rep}_$TAG 300 python -u bench.py --workload corr \
-          --no-cpu-baseline --no-pcie --warmup 5 --steps 20
+          --warmup 5 --steps 20
         sleep ${IDLE:-8}
         SRCDSP_HIP_LIB=$L SRCDSP_CORR_MFMA_RB=1 step corrlib_benchrb1${rep}_$TAG 300 python -u bench.py --workload corr \
-          --no-cpu-baseline --no-pcie --warmup 5 --steps 20
+          --warmup 5 --steps 20
       done
       SRCDSP_HIP_LIB=$L step corrlib_prof_$TAG 300 rocprofv3 --kernel-trace --stats -d gpurun_out/corrlib_prof_$TAG -o run \
-        --output-format csv -- python3 bench.py --workload corr --no-cpu-baseline --no-pcie --warmup 5 --steps 20 ;;
+        --output-format csv -- python3 bench.py --workload corr --warmup 5 --steps 20 ;;
     mixlib)  # the mixmfma tuning library behind the product's C ABI: its own cases, the chain GPU tests,
              # then config 4's bench line beside the product's
       L=$PWD/scripts/tune/ab/libsrcdsp_hip_mixmfma.so
@@ -147,39 +148,39 @@ for s in ${STEPS:-smoke tests bench}; do
         --timeout-method thread --maxfail=30 -k "chain or mixdecim or config4 or mixer or pipeline or streams or decim"
       for rep in 1 2; do
         sleep ${IDLE:-8}
-        step mixlib_benchprod${rep}_$TAG 300 python -u bench.py --workload mixdecim --no-cpu-baseline --no-pcie \
+        step mixlib_benchprod${rep}_$TAG 300 python -u bench.py --workload mixdecim \
           --warmup 5 --steps 20
         sleep ${IDLE:-8}
-        SRCDSP_HIP_LIB=$L step mixlib_bench${rep}_$TAG 300 python -u bench.py --workload mixdecim --no-cpu-baseline \
-          --no-pcie --warmup 5 --steps 20
+        SRCDSP_HIP_LIB=$L step mixlib_bench${rep}_$TAG 300 python -u bench.py --workload mixdecim \
+          --warmup 5 --steps 20
       done
       for rep in 1 2; do  # row a2 (the plain decimator) through the same kernel
         sleep ${IDLE:-8}
-        step mixlib_a2prod${rep}_$TAG 300 python -u bench.py --workload ci16decim --no-cpu-baseline --no-pcie \
+        step mixlib_a2prod${rep}_$TAG 300 python -u bench.py --workload ci16decim \
           --warmup 5 --steps 20
         sleep ${IDLE:-8}
-        SRCDSP_HIP_LIB=$L step mixlib_a2${rep}_$TAG 300 python -u bench.py --workload ci16decim --no-cpu-baseline \
-          --no-pcie --warmup 5 --steps 20
+        SRCDSP_HIP_LIB=$L step mixlib_a2${rep}_$TAG 300 python -u bench.py --workload ci16decim \
+          --warmup 5 --steps 20
       done
-      SRCDSP_HIP_LIB=$L step mixlib_steady_$TAG 300 python -u bench.py --workload mixdecim --no-cpu-baseline --no-pcie \
+      SRCDSP_HIP_LIB=$L step mixlib_steady_$TAG 300 python -u bench.py --workload mixdecim \
         --warmup 100 --steps 50
-      step mixlib_steadyprod_$TAG 300 python -u bench.py --workload mixdecim --no-cpu-baseline --no-pcie \
+      step mixlib_steadyprod_$TAG 300 python -u bench.py --workload mixdecim \
         --warmup 100 --steps 50
       SRCDSP_HIP_LIB=$L step mixlib_prof_$TAG 300 rocprofv3 --kernel-trace --stats -d gpurun_out/mixlib_prof_$TAG -o run \
-        --output-format csv -- python3 bench.py --workload mixdecim --no-cpu-baseline --no-pcie --warmup 5 --steps 20 ;;
+        --output-format csv -- python3 bench.py --workload mixdecim --warmup 5 --steps 20 ;;
     libpmc)  # MFMA-busy / clock counters of the two C-ABI matrix-core builds' kernels (PMC_PASSES, default MFMA + traffic)
       SRCDSP_HIP_LIB=$PWD/scripts/tune/ab/libsrcdsp_hip_corrmfma.so PMC_PASSES=${PMC_PASSES:-0,4,5} step libpmc_corr_$TAG 400 \
         python -u scripts/tune/pmc_cmd.py gpurun_out/libpmc_corr_$TAG.json corr_scan_mfma \
-        -- python3 bench.py --workload corr --no-cpu-baseline --no-parity --warmup 2 --steps 8
+        -- python3 bench.py --workload corr --warmup 2 --steps 8
       SRCDSP_HIP_LIB=$PWD/scripts/tune/ab/libsrcdsp_hip_mixmfma.so PMC_PASSES=${PMC_PASSES:-0,4,5} step libpmc_mix_$TAG 400 \
         python -u scripts/tune/pmc_cmd.py gpurun_out/libpmc_mix_$TAG.json mixdecim_mfma_step_i8 \
-        -- python3 bench.py --workload mixdecim --no-cpu-baseline --no-pcie --no-parity --warmup 2 --steps 8 ;;
+        -- python3 bench.py --workload mixdecim --warmup 2 --steps 8 ;;
     pg1)  # the N > 1 path on the real backend at one rank (torchrun, RCCL process group, device collectives,
           # the share's gather and its digests; bench.py SRCDSP_BENCH_PG=1)
       SRCDSP_BENCH_PG=1 step pg1_decim_$TAG 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 \
-        --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 1 --share --steps 5 --warmup 2 --no-cpu-baseline --no-pcie
+        --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 1 --full --share --steps 5 --warmup 2 --no-cpu-baseline --no-pcie
       SRCDSP_BENCH_PG=1 step pg1_corr_$TAG 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 \
-        --master-addr 127.0.0.1 --master-port 29612 bench.py --gpus 1 --workload corr --steps 5 --warmup 2 --no-cpu-baseline ;;
+        --master-addr 127.0.0.1 --master-port 29612 bench.py --gpus 1 --workload corr --steps 5 --warmup 2 ;;
     cpp) step cpp_$TAG 600 python -u -m pytest tests/test_dropin_cpp.py -m gpu -v --timeout 240 --timeout-method thread ;;
     *) echo "unknown step $s"; exit 2 ;;
   esac

@@ -25,7 +25,7 @@ def one(workload, ksub, counters, tag, extra):
     out = os.path.join(ROOT, "gpurun_out", "pmcw", f"{tag}_{workload}")
     cmd = ["timeout", "-s", "KILL", "90", "rocprofv3", "--pmc", *counters, "--kernel-trace", "--output-format",
            "csv", "-d", out, "-o", "p", "--", sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload,
-           "--steps", "10", "--warmup", "2", "--no-cpu-baseline", "--no-pcie", *extra]
+           "--steps", "10", "--warmup", "2", *extra]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise SystemExit(f"pass failed rc={r.returncode}: {r.stderr[-2000:]}")

@@ -102,7 +102,7 @@ def test_gpus_n_dry_run_world_and_labels(n):
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["OMP_NUM_THREADS"] = "1"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--dry-run"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--dry-run", "--full"],
                        capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
@@ -118,10 +118,10 @@ def test_gpus_n_dry_run_world_and_labels(n):
                                          f"configs[2] per-GPU layout ({8 * n} of 64 channels)")
 
 
-def _host_ranks(n, extra_env=None, args=()):
+def _host_ranks(n, extra_env=None, args=(), full=True):
     """Run tests/bench_host_rank.py as n gloo ranks (the driver's `bench.py
-    --gpus n` path with host stand-ins for the operators and the device) and
-    return rank 0's JSON line."""
+    --gpus n --full` path with host stand-ins for the operators and the
+    device; full=False: the plain run) and return rank 0's JSON line."""
     import json
     import socket
     import subprocess
@@ -132,7 +132,8 @@ def _host_ranks(n, extra_env=None, args=()):
     env.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), WORLD_SIZE=str(n), OMP_NUM_THREADS="1",
                **(extra_env or {}))
     cmd = [sys.executable, os.path.join(ROOT, "tests", "bench_host_rank.py"), "--gpus", str(n),
-           "--samples", str(1 << 20), "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-pcie", *args]
+           "--samples", str(1 << 20), "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-pcie", *(["--full"] if full else []),
+           *args]
     procs = [subprocess.Popen(cmd, env=dict(env, RANK=str(r), LOCAL_RANK=str(r)), stdout=subprocess.PIPE,
                               stderr=subprocess.PIPE, text=True) for r in range(n)]
     outs = [p.communicate(timeout=300) for p in procs]
@@ -213,6 +214,94 @@ def test_bench_main_one_rank_process_group_rehearsal():
     sh = line["configs2_share"]
     assert sh["gather_bytes"] == 8 * (1 << 18) * 8 and sh["gather_ms"] > 0
     assert (sh["gather_parity"]["channels_checked"], sh["gather_parity"]["mismatches"]) == (8, 0)
+
+
+def test_plain_run_has_only_the_headline_legs(tmp_path):
+    """Without --full the line keeps `value`, `ms_per_step` and the roofline
+    of the timed steps, and none of the legs that take runs of their own; the
+    parser turns every such leg off, whatever the other switches say.  At
+    N = 2 every rank dumps its own channel's output into the one directory."""
+    import numpy as np
+    line = _host_ranks(2, args=("--dump-outputs", str(tmp_path)), full=False)
+    assert sorted(os.listdir(tmp_path)) == ["y_rank0.npy", "y_rank1.npy"]
+    y0, y1 = (np.load(tmp_path / f"y_rank{r}.npy") for r in (0, 1))
+    assert y0.shape == y1.shape == (1 << 18, 2) and not np.array_equal(y0, y1)
+    assert line["n_gpus"] == 2 and line["steps"] == 2 and line["warmup"] == 1
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["unit"] == "Msamples/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "f32" and line["metric"] == bench.METRIC
+    assert line["roofline"]["kernel_ms"] > 0
+    for leg in ("parity", "configs2_share", "cpu_baseline", "cpu_baseline_allcores", "cpu_baseline_O0",
+                "pcie_inclusive"):
+        assert leg not in line, leg
+    plain = bench.parse(["--steps", "7", "--warmup", "3"])
+    assert plain.steps == 7 and plain.warmup == 3 and not plain.full
+    assert plain.no_cpu_baseline and plain.no_pcie and plain.no_parity and plain.no_share
+    full = bench.parse(["--full"])
+    assert not (full.no_cpu_baseline or full.no_pcie or full.no_parity or full.no_share)
+    assert bench.parse(["--full", "--no-pcie"]).no_pcie
+    assert bench.parse(["--share"]).no_share  # the share is another configuration: --full only
+    both = bench.parse(["--full", "--share"])
+    assert both.share and not both.no_share
+
+
+def test_dump_outputs_is_the_last_timed_step_and_repeats(tmp_path):
+    """--dump-outputs: y.npy holds what the third of three chained steps
+    (1 warm-up + 2 timed) over the seeded channel wrote, as float32 (re, im)
+    rows, bit for bit the oracle's; a second run writes the same bytes."""
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "oracle"))
+    import pyoracle
+    from srcdsp_amd.design import hamming_sinc
+    a, b = str(tmp_path / "a"), str(tmp_path / "b")
+    line = _host_ranks(1, args=("--dump-outputs", a), full=False)
+    _host_ranks(1, args=("--dump-outputs", b), full=False)
+    n = 1 << 20
+    assert line["dumped_outputs"] == {"y.npy": {"rows": n // 4, "of": n // 4, "dtype": "float32"}}
+    assert os.listdir(a) == ["y.npy"]
+    y = np.load(os.path.join(a, "y.npy"))
+    assert y.dtype == np.float32 and y.shape == (n // 4, 2)
+    assert np.array_equal(y.view(np.uint32), np.load(os.path.join(b, "y.npy")).view(np.uint32))
+    o = pyoracle.Oracle(1)
+    x = o.gen_cf32(bench.SEED, 0, 0, n)
+    f = o.decim(0, 4, hamming_sinc(127))
+    for _ in range(3):
+        want = f.step(x)
+    assert np.array_equal(y.view(np.uint32).reshape(-1), want.view(np.uint32).reshape(-1))
+
+
+def test_dump_outputs_samples_a_large_output_within_the_budget(tmp_path, monkeypatch):
+    """An output above its share of the budget is cut to a fixed, seeded row
+    sample: one row from each of k strata that tile all n rows (the last
+    rows included), the same rows in every call, taken from the tensor as it
+    stands; int32 goes out as float64.  The budget covers all ranks' files
+    together."""
+    import numpy as np
+    import torch
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 2 * 1000 * 8)  # 1000 rows of 2 float32 per output
+    n = 10999
+    y = torch.arange(2 * n, dtype=torch.float32).reshape(n, 2)
+    z = torch.arange(5, dtype=torch.int32)
+    work = types.SimpleNamespace(outputs=lambda: {"y": torch.view_as_complex(y), "z": z})
+    for d in ("a", "b"):
+        w = bench.dump_outputs(work, str(tmp_path / d), 0, 1, torch)
+    assert w == {"y.npy": {"rows": 1000, "of": n, "dtype": "float32"},
+                 "z.npy": {"rows": 5, "of": 5, "dtype": "float64"}}
+    got = np.load(tmp_path / "a" / "y.npy")
+    assert np.array_equal(got, np.load(tmp_path / "b" / "y.npy"))
+    rows = (got[:, 0] / 2).astype(np.int64)
+    assert np.array_equal(got[:, 1], got[:, 0] + 1)  # whole rows of the output
+    lo = np.arange(1001) * n // 1000  # strata [lo[i], lo[i+1]) tile 0..n
+    assert np.all(lo[:-1] <= rows) and np.all(rows < lo[1:])  # one row from each
+    assert rows[-1] >= n - 11  # the last stratum is the output's last rows
+    assert len(set(rows - lo[:-1])) > 1  # drawn within the stratum, not its first row
+    assert np.array_equal(np.load(tmp_path / "a" / "z.npy"), np.arange(5.0).reshape(5, 1))
+    for r in range(2):  # two ranks into one directory: half the rows each, the sum within the budget
+        w = bench.dump_outputs(work, str(tmp_path / "c"), r, 2, torch)
+        assert w == {f"y_rank{r}.npy": {"rows": 500, "of": n, "dtype": "float32"},
+                     f"z_rank{r}.npy": {"rows": 5, "of": 5, "dtype": "float64"}}
+    files = sorted(os.listdir(tmp_path / "c"))
+    assert files == ["y_rank0.npy", "y_rank1.npy", "z_rank0.npy", "z_rank1.npy"]
+    assert sum(np.load(tmp_path / "c" / f).nbytes for f in files) <= bench.DUMP_BUDGET_BYTES
 
 
 def test_host_leg_reports_a_failure_instead_of_raising():

@@ -66,7 +66,7 @@ int main() { return 0; }
     "dsptl::FilterDnsamplingFir<float, float, float, float, 4>",        # dsptl_dnsampling_filters.h:215
     "FilterFir<float, float, float, float>",                            # filters.h:164
     "dsptl::FilterUpsamplingFir<std::complex<float>, std::complex<float>, std::complex<float>, float, 4>",
-])
+], ids=lambda s: s.replace("::", "."))  # "::" separates the parts of a pytest node id: keep it out of the case ids
 def test_dropin_rejects_what_the_reference_cannot_compile(tmp_path, inst):
     src = ('#include "dnsampling_filters.h"\n#include "filters.h"\n#include "upsampling_filters.h"\n'
            f"template class {inst};\nint main(){{return 0;}}\n")

@@ -83,7 +83,7 @@ def test_two_ranks_on_gpu_match_single_process(tmp_path, pat_at):
 
 
 def test_bench_two_rank_rehearsal_default_layout():
-    """`bench.py --gpus 2` as the driver runs it, both ranks on cuda:0
+    """`bench.py --gpus 2 --full` as the driver runs it, both ranks on cuda:0
     (collectives rehearsed over gloo: two ranks on one device cannot form an
     RCCL communicator): the main series is one 2^28 channel per rank (the
     N = 1 line's work per GPU, weak scaling); `configs2_share` beside it runs
@@ -98,7 +98,7 @@ def test_bench_two_rank_rehearsal_default_layout():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["SRCDSP_BENCH_BACKEND"] = "gloo"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3",
-                        "--warmup", "1", "--no-cpu-baseline", "--no-pcie"],
+                        "--warmup", "1", "--full", "--no-cpu-baseline", "--no-pcie"],
                        capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
