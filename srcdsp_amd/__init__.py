@@ -16,7 +16,10 @@ from .operators import (  # noqa: F401
     MixerDecimatorChain,
     decim_step_batched,
     fill_synthetic,
+    mixdecim_batched_stats,
+    mixdecim_step_batched,
 )
 
 __all__ = ["FifoWithTimeTrack", "files", "FilterDnsamplingFir", "FilterFir", "FilterUpsamplingFir", "Mixer", "MixerDecimatorChain",
-           "FixedPatternCorrelator", "decim_step_batched", "fill_synthetic", "SrcdspError", "lib"]
+           "FixedPatternCorrelator", "decim_step_batched", "mixdecim_step_batched", "mixdecim_batched_stats",
+           "fill_synthetic", "SrcdspError", "lib"]

@@ -61,6 +61,8 @@ SIGNATURES = {
     "srcdsp_mixer_step": (I, [VP, VP, SZ, VP, VP]),
     "srcdsp_mixer_step_host": (I, [VP, VP, SZ, VP]),
     "srcdsp_mixdecim_step": (I, [VP, VP, VP, SZ, VP, SZ, VP]),
+    "srcdsp_mixdecim_step_batched": (I, [HP, HP, I, VP, SZ, VP, SZ, SZ, VP]),
+    "srcdsp_mixdecim_batched_stats": (I, [C.POINTER(C.c_ulong), C.POINTER(C.c_ulong)]),
     "srcdsp_corr_create": (I, [HP, U, U]),
     "srcdsp_corr_destroy": (I, [VP]),
     "srcdsp_corr_clone": (I, [VP, HP]),

@@ -1,0 +1,163 @@
+// ddc_bank.hip -- srcdsp_mixdecim_step_batched: C mixer -> decimator chains in
+// one call (a digital down-converter bank: one wideband input or one input per
+// channel, C local oscillators, one shared channel filter).
+//
+// Dispatch.  The bank kernel (ddc_bank_kernels.h) takes: variant 1
+// (complex<int16_t>, int32 taps all in int16 range), M = 4, 1..1024 taps, a
+// mixer table of N = 2^k <= 4096 entries, a 16-byte aligned input and input
+// row stride (output rows need only their samples' 4-byte alignment: a row of
+// n_in / 4 outputs is a multiple of 16 bytes only for some n_in), and
+// n_in x taps <= 2^31 per channel (kBankMaxWork below: past it the loop's
+// per-frequency register table wins).  Every other shape -- other M, taps
+// beyond int16, variant 2, other N, misaligned input views, longer calls -- is
+// the loop of srcdsp_mixdecim_step over the channels.
+// Either way the outputs and every handle's state (mixer phase, decimator
+// history) are those of that loop, bit for bit.
+#include <algorithm>
+#include <atomic>
+#include <vector>
+
+#include "ops.h"
+
+#include "ddc_bank_kernels.h"
+
+namespace srcdsp {
+namespace {
+std::atomic<unsigned long> g_bank_calls{0}, g_loop_calls{0};
+
+bool al16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
+
+// persistent grid: the resident capacity (256 CUs x 4 workgroups) twice over
+constexpr long kBankGridCap = 2048;
+
+// The bank kernel's one general mixer table costs ~12 VALU operations per
+// sample and channel where the single-channel kernel's per-frequency register
+// table costs ~3, so once a call is long enough to hide the loop's launches
+// behind its kernels and the tap loop is VALU-bound, the loop is faster.
+// Measured on MI355X (8 channels, bank / loop time per step): n_in x taps =
+// 2.1e9: 0.91 (31 taps, 2^26 samples), 0.96 (127 taps, 2^24); 4.3e9: 1.07
+// (63 taps, 2^26), 1.005 (255 taps, 2^24), 1.05 (1024 taps, 2^22); 8.5e9: 1.25
+// (127 taps, 2^26).  Below the bound the bank is 0.33-0.84 of the loop.
+constexpr unsigned long kBankMaxWork = 1ul << 31;  // n_in x taps per channel
+
+bool bank_takes(const FirCore &f, const MixerState &m, const void *d_in, size_t in_stride, size_t n_in) {
+    return f.kv == KV_CI16_I32 && f.M == 4 && f.coef_fits_i16 && f.ntaps >= 1 && f.ntaps <= kDot2MaxTaps &&
+           m.N >= 4 && m.N <= (unsigned)kBankMaxN && (m.N & (m.N - 1)) == 0 && al16(d_in) &&
+           (in_stride * 4) % 16 == 0 && n_in <= kBankMaxWork / (unsigned long)f.ntaps;
+}
+
+int bank_launch(const srcdsp_mixer_t *mixers, const srcdsp_decim_t *decims, int nc, const void *d_in, size_t in_stride,
+                void *d_out, size_t out_stride, size_t n_in, hipStream_t s) {
+    FirCore &f0 = decims[0]->core;
+    BankLaunch L{};
+    L.in = d_in;
+    L.out = d_out;
+    L.cpair = f0.d_cpair;
+    L.table = mixers[0]->m.d_table;  // one table for all: built from N alone (mixers.h:155-158)
+    L.n_in = (long)n_in;
+    L.n_out = (long)(n_in / 4);
+    L.in_stride = (long)in_stride;
+    L.out_stride = (long)out_stride;
+    L.ntiles = (L.n_out + kBankTO - 1) / kBankTO;
+    L.ntaps = f0.ntaps;
+    L.shift = f0.shift();
+    L.N = mixers[0]->m.N;
+    L.channels = nc;
+    // a shared input: a workgroup serves a group of channels from one fetch of
+    // the tile; the group shrinks while the grid would not fill the device
+    int group = 1;
+    if (in_stride == 0) {
+        group = std::min(kBankGroup, nc);
+        while (group > 1 && L.ntiles * ((nc + group - 1) / group) < kBankGridCap / 2) group = (group + 1) / 2;
+    }
+    L.group = group;
+    const int ngroups = (nc + group - 1) / group;
+    for (int c = 0; c < nc; ++c) {
+        MixerState &m = mixers[c]->m;
+        FirCore &fc = decims[c]->core;
+        int rc = m.order.before(s);
+        if (!rc) rc = fc.order.before(s);
+        if (rc) return rc;
+        L.mix[c] = (uint32_t)(uint16_t)m.phi | ((uint32_t)(uint16_t)m.freq << 16);
+        L.hist_in[c] = fc.d_hist[fc.cur];
+        L.hist_out[c] = fc.d_hist[fc.cur ^ 1];
+    }
+    dim3 grid((unsigned)std::min<long>(L.ntiles, std::max<long>(1, kBankGridCap / ngroups)), (unsigned)ngroups);
+    hipLaunchKernelGGL(ddc_bank_ci16, grid, dim3(kBankBlock), 0, s, L);
+    SRCDSP_HIP_TRY(hipGetLastError());
+    for (int c = 0; c < nc; ++c) {
+        MixerState &m = mixers[c]->m;
+        FirCore &fc = decims[c]->core;
+        fc.cur ^= 1;
+        // mixer phase after the call: phi += n_in * freq (mod N), mixers.h:177
+        m.phi = (int16_t)(((unsigned long)(unsigned)m.phi + (unsigned long)(n_in % m.N) * (unsigned)m.freq) % m.N);
+        int rc = m.order.after(s);
+        if (!rc) rc = fc.order.after(s);
+        if (rc) return rc;
+    }
+    return SRCDSP_OK;
+}
+}  // namespace
+}  // namespace srcdsp
+
+using namespace srcdsp;
+
+extern "C" {
+
+SRCDSP_API int srcdsp_mixdecim_step_batched(const srcdsp_mixer_t *mixers, const srcdsp_decim_t *decims, int channels,
+                                            const void *d_in, size_t in_stride, void *d_out, size_t out_stride,
+                                            size_t n_in, void *stream) {
+    SRCDSP_ARG_CHECK(mixers != nullptr && decims != nullptr && channels >= 1, "mixdecim_step_batched: no handles");
+    for (int c = 0; c < channels; ++c)
+        SRCDSP_ARG_CHECK(mixers[c] != nullptr && decims[c] != nullptr, "mixdecim_step_batched: null handle");
+    const FirCore &f0 = decims[0]->core;
+    const MixerState &m0 = mixers[0]->m;
+    if (f0.kv != KV_CI16_I32 && f0.kv != KV_CI16_I16) {
+        set_error("mixdecim_step_batched: the decimators must take complex<int16_t> input (the mixer's output)");
+        return SRCDSP_ERR_UNSUPPORTED;
+    }
+    for (int c = 1; c < channels; ++c) {
+        const FirCore &fc = decims[c]->core;
+        SRCDSP_ARG_CHECK(fc.kv == f0.kv && fc.M == f0.M && fc.ntaps == f0.ntaps && fc.flags == f0.flags &&
+                             fc.shift() == f0.shift() && fc.h_coef == f0.h_coef,
+                         "mixdecim_step_batched: decimators must share variant, M, taps, flags and shift");
+        SRCDSP_ARG_CHECK(mixers[c]->m.N == m0.N, "mixdecim_step_batched: mixers must share N");
+    }
+    {
+        std::vector<const void *> hm(mixers, mixers + channels), hd(decims, decims + channels);
+        std::sort(hm.begin(), hm.end());
+        std::sort(hd.begin(), hd.end());
+        SRCDSP_ARG_CHECK(std::adjacent_find(hm.begin(), hm.end()) == hm.end() &&
+                             std::adjacent_find(hd.begin(), hd.end()) == hd.end(),
+                         "mixdecim_step_batched: every handle may be listed once");
+    }
+    SRCDSP_ARG_CHECK(n_in % f0.M == 0, "mixdecim_step_batched: n_in must be a multiple of M");
+    if (n_in == 0) return SRCDSP_OK;
+    SRCDSP_ARG_CHECK(d_in && d_out, "mixdecim_step_batched: null buffer");
+    hipStream_t s = (hipStream_t)stream;
+    if (!bank_takes(f0, m0, d_in, in_stride, n_in)) {
+        g_loop_calls.fetch_add(1, std::memory_order_relaxed);
+        for (int c = 0; c < channels; ++c) {
+            int rc = srcdsp_mixdecim_step(mixers[c], decims[c], (const char *)d_in + (size_t)c * in_stride * 4, n_in,
+                                          (char *)d_out + (size_t)c * out_stride * 4, n_in / f0.M, stream);
+            if (rc) return rc;
+        }
+        return SRCDSP_OK;
+    }
+    g_bank_calls.fetch_add(1, std::memory_order_relaxed);
+    for (int c0 = 0; c0 < channels; c0 += kMaxBatch) {
+        const int nc = std::min(kMaxBatch, channels - c0);
+        int rc = bank_launch(mixers + c0, decims + c0, nc, (const char *)d_in + (size_t)c0 * in_stride * 4, in_stride,
+                             (char *)d_out + (size_t)c0 * out_stride * 4, out_stride, n_in, s);
+        if (rc) return rc;
+    }
+    return SRCDSP_OK;
+}
+
+SRCDSP_API int srcdsp_mixdecim_batched_stats(unsigned long *bank_calls, unsigned long *loop_calls) {
+    if (bank_calls) *bank_calls = g_bank_calls.load(std::memory_order_relaxed);
+    if (loop_calls) *loop_calls = g_loop_calls.load(std::memory_order_relaxed);
+    return SRCDSP_OK;
+}
+
+}  // extern "C"

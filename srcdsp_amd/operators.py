@@ -389,6 +389,41 @@ class MixerDecimatorChain:
         return out
 
 
+def mixdecim_step_batched(mixers, decims, inp, out):
+    """Step C mixer -> decimator chains in one call (a DDC bank): channel c is
+    exactly ``MixerDecimatorChain(mixers[c], decims[c]).step``.  ``inp`` of
+    shape (L,) samples is one input shared by every channel (read once); of
+    shape (C, L) one row per channel.  ``out`` is (C, L // M).  Device tensors
+    of complex<int16_t> samples (int16 [..., 2])."""
+    ch = len(mixers)
+    if ch < 1 or len(decims) != ch:
+        raise ValueError("DDC bank: need one decimator per mixer, at least one channel")
+    if not (_is_device(inp) and _is_device(out)):
+        raise ValueError("DDC bank: device tensors only")
+    if inp.dim() not in (2, 3) or inp.shape[-1] != 2 or out.dim() != 3 or out.shape[-1] != 2:
+        raise ValueError("DDC bank: inp is int16 [L, 2] (shared) or [C, L, 2], out int16 [C, L // M, 2]")
+    shared = inp.dim() == 2
+    if not shared and inp.shape[0] != ch:
+        raise ValueError("DDC bank: one input row per channel")
+    n_in = inp.shape[-2]
+    M = decims[0].M
+    if out.shape[0] != ch or out.shape[1] * M != n_in:
+        raise ValueError("DDC bank: out must be [C, L // M] with L a multiple of M")
+    hm = (C.c_void_p * ch)(*[m._h.value for m in mixers])
+    hd = (C.c_void_p * ch)(*[d._h.value for d in decims])
+    A.call("srcdsp_mixdecim_step_batched", hm, hd, ch, _ptr(inp), 0 if shared else n_in, _ptr(out), out.shape[1],
+           n_in, _stream(inp))
+    return out
+
+
+def mixdecim_batched_stats():
+    """(bank_calls, loop_calls): batched calls served by the DDC bank kernel and
+    by the per-channel loop, process-wide."""
+    b, l = C.c_ulong(), C.c_ulong()
+    A.call("srcdsp_mixdecim_batched_stats", C.byref(b), C.byref(l))
+    return b.value, l.value
+
+
 # ======================================================== FixedPatternCorrelator
 class FixedPatternCorrelator(_Handle):
     """dsptl::FixedPatternCorrelator<int16_t, int32_t, N, S> (correlators.h:54-316)."""
