@@ -40,7 +40,7 @@
 // between re and im.  With that, the 16 lanes of each ds_read_b128 lane group
 // hit 16 distinct 16-B bank slots for every read (checked exhaustively).
 #pragma once
-#include "../../srcdsp_amd/csrc/decim_kernels.h"
+#include "../../srcdsp_amd/csrc/fir_device.h"
 
 namespace srcdsp {
 

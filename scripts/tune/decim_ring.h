@@ -20,7 +20,7 @@
 // Wave tile order: chunks of CH consecutive wave tiles per workgroup, the
 // chunks grid-strided over the (XCD-mapped) workgroups.
 #pragma once
-#include "../../srcdsp_amd/csrc/decim_kernels.h"
+#include "../../srcdsp_amd/csrc/decim_cf32_kernels.h"
 
 namespace srcdsp {
 

@@ -2,9 +2,9 @@
 // The headline complex<float> decimator with every knob the tuning rounds
 // varied (probe paths, cache-policy overrides, store shapes, issue order),
 // plus the measured-and-rejected wave-private variant.  The product kernel is
-// srcdsp_amd/csrc/decim_kernels.h decim_stream_cf32 (no knobs).
+// srcdsp_amd/csrc/decim_cf32_kernels.h decim_stream_cf32 (no knobs).
 #pragma once
-#include "../../srcdsp_amd/csrc/decim_kernels.h"
+#include "../../srcdsp_amd/csrc/decim_cf32_kernels.h"
 
 namespace srcdsp {
 // OST: 0 = each lane stores its own R outputs (two 16-B stores at a 32-B lane

@@ -1,9 +1,11 @@
 // Tuning harness (not part of the product): instantiates decimator kernel
-// variants from srcdsp_amd/csrc/decim_kernels.h and an FMA-rate microbenchmark
-// so they can be timed side by side, interleaved, in one process.
+// variants from srcdsp_amd/csrc (decim_cf32_kernels.h, fir_f32_kernels.h) and
+// an FMA-rate microbenchmark so they can be timed side by side, interleaved,
+// in one process.
 #include "decim_tune.h"
 #include "decim_mfma.h"
 #include "decim_ring.h"
+#include "../../srcdsp_amd/csrc/fir_f32_kernels.h"
 
 using namespace srcdsp;
 

@@ -49,7 +49,7 @@ sys.path.insert(0, ROOT)
 from srcdsp_amd import build as B  # noqa: E402
 
 PATCHES = {
-    "halflds": [("decim_kernels.h", """            auto load_group = [&](int e) {
+    "halflds": [("decim_cf32_kernels.h", """            auto load_group = [&](int e) {
                 const float4 g0 = rd(Bt + 2 * e + floordiv(2 * e, PR));
                 const float4 g1 = rd(Bt + 2 * e + 1 + floordiv(2 * e + 1, PR));""",
                  """            auto load_group = [&](int e) {
@@ -61,7 +61,7 @@ PATCHES = {
                     asm volatile("" : "=v"(g0.x), "=v"(g0.y), "=v"(g0.z), "=v"(g0.w));
                     asm volatile("" : "=v"(g1.x), "=v"(g1.y), "=v"(g1.z), "=v"(g1.w));
                 }""")],
-    "r8": [("decim_kernels.h", """    static_assert((M * R) % 4 == 0 && M * R <= 16, "a lane chunk is 4, 8, 12 or 16 input samples");""",
+    "r8": [("decim_cf32_kernels.h", """    static_assert((M * R) % 4 == 0 && M * R <= 16, "a lane chunk is 4, 8, 12 or 16 input samples");""",
             """    static_assert((M * R) % 4 == 0 && M * R <= 32, "a lane chunk is 4 to 32 input samples");"""),
            ("cf32_launch.h", """template <int NT, int M = 4>
 int launch_cf32(DecimLaunch L, int channels, bool fma, hipStream_t s) {
@@ -87,7 +87,7 @@ int launch_cf32(""")
            # the compiled-tap window in EH + 3 rotating group slots (as the
            # runtime-tap path): the flat 4 (NQ + GPC) array is not promoted to
            # registers at GPC = 8
-           , ("decim_kernels.h", """            float2 X[4 * (NQC + GPC)];
+           , ("decim_cf32_kernels.h", """            float2 X[4 * (NQC + GPC)];
             auto load_group = [&](int e) {
                 const float4 g0 = rd(Bt + 2 * e + floordiv(2 * e, PR));
                 const float4 g1 = rd(Bt + 2 * e + 1 + floordiv(2 * e + 1, PR));
@@ -106,7 +106,7 @@ int launch_cf32(""")
                 X[slot(e)][2] = make_float2(g1.x, g1.y);
                 X[slot(e)][3] = make_float2(g1.z, g1.w);
             };"""),
-           ("decim_kernels.h", """                auto xs = [&](int r, int p) { return X[M * r - 4 * q - p + 4 * NQC]; };""",
+           ("decim_cf32_kernels.h", """                auto xs = [&](int r, int p) { return X[M * r - 4 * q - p + 4 * NQC]; };""",
             """                auto xs = [&](int r, int p) {
                     const int s = M * r - 4 * q - p;
                     return X[slot(floordiv(s, 4))][s - 4 * floordiv(s, 4)];
@@ -114,7 +114,7 @@ int launch_cf32(""")
     "r4mix": [("decim.hip", """    if constexpr (BLOCK == 512)
         if ((16u * BLOCK) % pe == 0) return""", """    if constexpr (false)
         if ((16u * BLOCK) % pe == 0) return"""),
-              ("decim_kernels.h", """                    if (j == 0) {
+              ("decim_ci16_kernels.h", """                    if (j == 0) {
                         yr[r] = sdot2_0(Dr[OFF + 2 * r], P);
                         yi[r] = sdot2_0(Di[OFF + 2 * r], P);
                     } else {""", """                    if (j == 0) {

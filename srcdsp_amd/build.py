@@ -42,9 +42,12 @@ def _headers() -> list[str]:
     return glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(ROOT, "include", "srcdsp_hip.h")]
 
 
-# the translation unit that holds each bench workload's dominant kernel
-WORKLOAD_TU = {"decim": "decim.hip", "mixdecim": "decim.hip", "ci16decim": "decim.hip", "fir": "decim.hip",
-               "up": "upsamp.hip", "corr": "corr.hip", "fifo": "fifo.hip", "iq": "fifo.hip"}
+# the translation units that hold or launch each bench workload's dominant
+# kernel (decim: dispatched in decim.hip, instantiated and launched in the two
+# decim_cf32 units)
+WORKLOAD_TU = {"decim": ("decim.hip", "decim_cf32_ct.hip", "decim_cf32_rt.hip"),
+               "mixdecim": ("decim.hip",), "ci16decim": ("decim.hip",), "fir": ("decim.hip",),
+               "up": ("upsamp.hip",), "corr": ("corr.hip",), "fifo": ("fifo.hip",), "iq": ("fifo.hip",)}
 
 
 def _tu_files(tu: str) -> list[str]:
@@ -71,12 +74,12 @@ def source_digest(workload: str | None = None) -> str:
     """sha256 (16 hex) over kernel sources: stamps measured evidence
     (profiles/pmc_traffic.json) with the code it was measured on, so a later
     change shows it as stale.  With a bench workload: only the translation
-    unit of its kernel and the headers that unit includes; without one: every
-    csrc/*.hip, csrc/*.h and the C ABI header."""
+    units of its kernel (WORKLOAD_TU) and the headers they include; without
+    one: every csrc/*.hip, csrc/*.h and the C ABI header."""
     import hashlib
     h = hashlib.sha256()
     if workload is not None:
-        files = sorted(_tu_files(WORKLOAD_TU[workload]))
+        files = sorted({f for tu in WORKLOAD_TU[workload] for f in _tu_files(tu)})
     else:
         files = sorted(glob.glob(os.path.join(CSRC, "*.hip")) + _headers())
     for f in files:

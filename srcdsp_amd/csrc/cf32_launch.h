@@ -10,7 +10,7 @@
 
 #include "ops.h"
 
-#include "decim_kernels.h"
+#include "decim_cf32_kernels.h"
 
 namespace srcdsp {
 

@@ -101,6 +101,9 @@ __device__ __forceinline__ ConstPtr<T> const_view(const void *p) {
 constexpr int floordiv(int a, int b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
 constexpr int ceildiv(int a, int b) { return (a + b - 1) / b; }
 
+// 16-byte alignment of a buffer, as the kernels' dwordx4 accesses need it
+inline bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
+
 // ------------------------------------------------------------ host copies
 // host memcpy into / out of pinned staging buffers, split over a persistent
 // pool of host threads for large copies (one thread cannot fill the host link)

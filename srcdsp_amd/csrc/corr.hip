@@ -20,7 +20,7 @@
 #include <vector>
 
 #include "ops.h"
-#include "decim_kernels.h"
+#include "fir_device.h"
 #include "corr_hit.h"
 
 namespace srcdsp {

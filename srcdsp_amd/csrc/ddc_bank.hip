@@ -25,8 +25,6 @@ namespace srcdsp {
 namespace {
 std::atomic<unsigned long> g_bank_calls{0}, g_loop_calls{0};
 
-bool al16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
-
 // persistent grid: the resident capacity (256 CUs x 4 workgroups) twice over
 constexpr long kBankGridCap = 2048;
 
@@ -42,7 +40,7 @@ constexpr unsigned long kBankMaxWork = 1ul << 31;  // n_in x taps per channel
 
 bool bank_takes(const FirCore &f, const MixerState &m, const void *d_in, size_t in_stride, size_t n_in) {
     return f.kv == KV_CI16_I32 && f.M == 4 && f.coef_fits_i16 && f.ntaps >= 1 && f.ntaps <= kDot2MaxTaps &&
-           m.N >= 4 && m.N <= (unsigned)kBankMaxN && (m.N & (m.N - 1)) == 0 && al16(d_in) &&
+           m.N >= 4 && m.N <= (unsigned)kBankMaxN && (m.N & (m.N - 1)) == 0 && aligned16(d_in) &&
            (in_stride * 4) % 16 == 0 && n_in <= kBankMaxWork / (unsigned long)f.ntaps;
 }
 

@@ -2,7 +2,7 @@
 // chains (mixers.h:169-188, dnsampling_filters.h:129-172) that share one
 // channel filter, and optionally one input, in a single launch.
 //
-// ddc_bank_ci16 is decim_dot2_ci16's run-time-tap form (decim_kernels.h) with
+// ddc_bank_ci16 is decim_dot2_ci16's run-time-tap form (decim_ci16_kernels.h) with
 // the channel as an inner loop: complex<int16_t> samples, int16-range taps as
 // v_dot2 tap pairs over planar int16 LDS images, M = 4, any tap count <= 1024,
 // a mixer table of N = 2^k <= 4096 entries.
@@ -33,7 +33,7 @@
 //    ping-pong buffer.
 // LDS: 20.25 KB plane image + 16 KB table = 36.25 KB, four workgroups per CU.
 #pragma once
-#include "decim_kernels.h"
+#include "fir_device.h"
 
 namespace srcdsp {
 
@@ -101,19 +101,11 @@ __global__ __launch_bounds__(kBankBlock, 4) void ddc_bank_ci16(BankLaunch a) {
 
     // mixers.h:169-188 on 4 consecutive samples, the first at phase ph
     auto mix4 = [&](uint4 w, unsigned ph, unsigned fr, uint2 &re, uint2 &im) {
-        int32_t r0, i0, r1, i1, r2, i2, r3, i3;
-        auto one = [&](uint32_t x, unsigned p, int32_t &r, int32_t &i) {
-            const uint32_t C = lut[bank_swz(p & mask)];
-            const uint32_t A = __builtin_bit_cast(uint32_t, __builtin_bit_cast(short2_t_, C) * (short2_t_){1, -1});
-            r = sdot2_0(x, A);
-            i = sdot2_0(__builtin_amdgcn_alignbit(x, x, 16), C);
-        };
-        one(w.x, ph, r0, i0);
-        one(w.y, ph + fr, r1, i1);
-        one(w.z, ph + 2 * fr, r2, i2);
-        one(w.w, ph + 3 * fr, r3, i3);
-        re = make_uint2(clamp_pair_s14(r0, r1), clamp_pair_s14(r2, r3));
-        im = make_uint2(clamp_pair_s14(i0, i1), clamp_pair_s14(i2, i3));
+        auto word = [&](unsigned p) { return lut[bank_swz(p & mask)]; };
+        int32_t r[4], i[4];
+        mix_granule_c(w, make_uint4(word(ph), word(ph + fr), word(ph + 2 * fr), word(ph + 3 * fr)), r, i);
+        re = clamp_granule_s14(r);
+        im = clamp_granule_s14(i);
     };
     auto lds_half = [&](int g, int plane) { return (uint2 *)&lds[dot2_slot<NC>(g >> 1, plane)] + (g & 1); };
 

@@ -6,7 +6,10 @@
 //   out[n] = limitScale16(y[n], coeffScaling - leftShift)
 // where x[<0] is the N-1 sample history carried from the previous call.
 //
-// Kernels (decim_kernels.h)
+// Kernels, one header per family over the shared helpers of fir_device.h:
+// decim_cf32_kernels.h (launched from decim_cf32_ct.hip / decim_cf32_rt.hip
+// through cf32_launch.h), decim_ci16_kernels.h, fir_f32_kernels.h and
+// decim_tile_kernels.h (launched from this unit).
 //  * decim_stream_cf32<NT,R,BLOCK,FMA,MINW,Q0,M> -- the headline path:
 //    complex<float>, M = 4, 127 taps (and M = 1/2/3/8/16, any N <= 1024 with
 //    NT = 0: the tap count at run time).  A persistent grid of 512-lane
@@ -20,9 +23,10 @@
 //    in ascending k (FMA) or separately rounded mul+add (!FMA).  Outputs are
 //    paired across the two half-waves (v_permlane32_swap) so each store
 //    instruction writes 1 KiB of whole lines, non-temporal.
-//  * decim_dot2_ci16<NT,BLOCK,MIX,MINW,TAB2> -- complex<int16_t> x int16-range
-//    taps on v_dot2 tap pairs over planar int16 LDS images, optionally with
-//    the NCO mixer of mixers.h fused into the staging pass (config 4).
+//  * decim_dot2_ci16<NT,BLOCK,MIX,MINW,TABM,MD> -- complex<int16_t> x
+//    int16-range taps on v_dot2 tap pairs over planar int16 LDS images (M = MD
+//    in 1/2/4/8/16), optionally with the NCO mixer of mixers.h fused into the
+//    staging pass (config 4; TABM: the mixer table form).
 //  * decim_stream_ci16<NT,R,BLOCK,MIX,MINW> -- the same for |c| < 2^23 taps
 //    (v_mad_i32_i24).
 //  * fir_stream_f32 / fir_tile_f32 -- M = 1 (FilterFir) for float input.
@@ -32,19 +36,17 @@
 // workgroup that owns tile 0 into the other ping-pong buffer, so a step is one
 // launch.
 #include <algorithm>
-#include <cstdlib>
 #include <vector>
 
 #include "ops.h"
 
-#include "decim_kernels.h"
+#include "decim_ci16_kernels.h"
+#include "decim_tile_kernels.h"
+#include "fir_f32_kernels.h"
 
 namespace srcdsp {
 
 // ============================================================== dispatch
-namespace {
-constexpr int kCiR_ = 4, kCiBlock_ = 256;
-}
 // phase advance of the fused mixer over `samples` input samples (one tile)
 unsigned phase_step(unsigned long N, unsigned long fr, unsigned long samples) {
     return (unsigned)((samples % N) * fr % N);
@@ -57,32 +59,28 @@ namespace {
 constexpr int kCfGridCap = 2048;  // persistent grid of the streaming kernels
 constexpr int kCiR = 4, kCiBlock = 256;
 
+// The fused mixer's phases that depend on the kernel's geometry: of tile 0's
+// first staged sample, -halo, and the advance over one tile of spt input
+// samples.  (phase of sample i: (phi0 + i*freq) mod N, for any sign of i)
+void set_mix_geometry(DecimLaunch &L, int halo, int spt) {
+    const unsigned long N = L.mix_N, h = (unsigned long)halo % N;
+    L.mix_phase_tile0 = (unsigned)((L.mix_phase0 + ((N - h) % N) * L.mix_freq) % N);
+    L.mix_dtile = phase_step(N, L.mix_freq, (unsigned long)spt);
+}
+
 template <int NT>
 int launch_ci16(DecimLaunch L, int channels, bool mixed, hipStream_t s) {
     constexpr int TO = kCiBlock * kCiR;
     L.ntiles = (L.n_out + TO - 1) / TO;
     dim3 grid((unsigned)std::min<long>(L.ntiles, kCfGridCap), channels);
-    if (mixed)
+    if (mixed) {
+        set_mix_geometry(L, ci16_halo(NT), ci16_spt(kCiBlock, kCiR));
         hipLaunchKernelGGL((decim_stream_ci16<NT, kCiR, kCiBlock, true, 4>), grid, dim3(kCiBlock), 0, s, L);
-    else
+    } else {
         hipLaunchKernelGGL((decim_stream_ci16<NT, kCiR, kCiBlock, false, 4>), grid, dim3(kCiBlock), 0, s, L);
+    }
     return SRCDSP_OK;
 }
-
-// dot2 ci16 kernel shape: tile lanes and mixer table form.  The product ships
-// one shape (512 lanes, sequence mixer table: measured best, profiles/); a
-// tuning build (-DSRCDSP_TUNING, scripts/tune) can pick another with
-// SRCDSP_CI16_VARIANT = 0: 256 lanes, 1: 512 lanes, 2: 256 lanes + doubled
-// table, 3: 512 lanes + doubled table, 4 (product): 512 lanes + sequence table.
-#ifdef SRCDSP_TUNING
-static int ci16_variant() {
-    static const int v = [] {
-        const char *e = std::getenv("SRCDSP_CI16_VARIANT");
-        return e ? std::atoi(e) : 4;
-    }();
-    return v;
-}
-#endif
 
 #ifdef SRCDSP_PHASE_CLOCK
 // tuning build: read (and clear) decim_dot2_ci16's phase clock sums
@@ -105,49 +103,39 @@ static unsigned mixer_seq_period(unsigned N, unsigned fr) {
 }
 constexpr unsigned kSeqMax = 4096;  // 2 x 4096 words of LDS, as the doubled phase table
 
+// one dot2 ci16 kernel shape: tile lanes and mixer table form (TABM = 0: the
+// unmixed kernel only)
 template <int NT, int BLOCK, int TABM, int MD = 4>
 int launch_ci16_dot2_shape(DecimLaunch L, int channels, bool mixed, hipStream_t s) {
-    constexpr int TO = BLOCK * dot2_r(MD), SPT = MD * TO;  // outputs / input samples per tile
+    constexpr int SPT = dot2_spt(BLOCK, MD), TO = SPT / MD;  // input samples / outputs per tile
     L.ntiles = (L.n_out + TO - 1) / TO;
-    if (mixed) L.mix_dtile = phase_step(L.mix_N, L.mix_freq, SPT);
-    if (mixed && NT == 0) {
-        // phase of tile 0's first staged sample, -dot2_rt_halo(N) (the
-        // caller's value is for the 127/128-tap halo of 128 samples)
-        const unsigned long N = L.mix_N, h = (unsigned long)dot2_rt_halo(L.ntaps) % N;
-        L.mix_phase_tile0 = (unsigned)((L.mix_phase0 + ((N - h) % N) * L.mix_freq) % N);
-    }
-    if (mixed && TABM >= 2) {
-        L.mix_pe = mixer_seq_period(L.mix_N, L.mix_freq);
-        L.mix_pe_dtile = (unsigned)((unsigned long)SPT % L.mix_pe);
-        L.mix_pe_drow = (unsigned)((4ul * BLOCK) % L.mix_pe);
-    }
     dim3 grid((unsigned)std::min<long>(L.ntiles, kCfGridCap * 256 / BLOCK), channels);
     // M = 1 (16 outputs per lane) needs more than 128 VGPRs: 3 waves per SIMD
     constexpr int MINW = MD == 1 ? 3 : 4;
-    if (mixed)
-        hipLaunchKernelGGL((decim_dot2_ci16<NT, BLOCK, true, MINW, TABM, MD>), grid, dim3(BLOCK), 0, s, L);
-    else
-        hipLaunchKernelGGL((decim_dot2_ci16<NT, BLOCK, false, MINW, 0, MD>), grid, dim3(BLOCK), 0, s, L);
+    if constexpr (TABM != 0) {
+        if (mixed) {
+            set_mix_geometry(L, dot2_halo(NT, L.ntaps), SPT);
+            if (TABM >= 3) {
+                L.mix_pe = mixer_seq_period(L.mix_N, L.mix_freq);
+                L.mix_pe_dtile = (unsigned)((unsigned long)SPT % L.mix_pe);
+                L.mix_pe_drow = (unsigned)((4ul * BLOCK) % L.mix_pe);
+            }
+            hipLaunchKernelGGL((decim_dot2_ci16<NT, BLOCK, true, MINW, TABM, MD>), grid, dim3(BLOCK), 0, s, L);
+            return SRCDSP_OK;
+        }
+    }
+    hipLaunchKernelGGL((decim_dot2_ci16<NT, BLOCK, false, MINW, 0, MD>), grid, dim3(BLOCK), 0, s, L);
     return SRCDSP_OK;
 }
 
+// The product shape: 512 lanes (M = 1: 256, 3 workgroups of 4 waves per CU).
+// Mixed: the two-word sequence mixer table (conflict-free reads for any
+// frequency, no per-sample negate or swap) when its period fits the LDS
+// budget, else the doubled phase table.
 template <int NT, int MD = 4>
 int launch_ci16_dot2(DecimLaunch L, int channels, bool mixed, hipStream_t s) {
-#ifdef SRCDSP_TUNING
-    switch (ci16_variant()) {
-    case 0: return launch_ci16_dot2_shape<NT, 256, 0>(L, channels, mixed, s);
-    case 1: return launch_ci16_dot2_shape<NT, 512, 0>(L, channels, mixed, s);
-    case 2: return launch_ci16_dot2_shape<NT, 256, 1>(L, channels, mixed, s);
-    case 3: return launch_ci16_dot2_shape<NT, 512, 1>(L, channels, mixed, s);
-    default: break;
-    }
-#endif
-    // the product shape: 512 lanes; the two-word sequence mixer table
-    // (conflict-free reads for any frequency, no per-sample negate or swap)
-    // when its period fits the LDS budget, else the doubled phase table
-    // (only these instantiations are compiled outside the tuning build)
-    constexpr int BLOCK = MD == 1 ? 256 : 512;  // M = 1: 3 workgroups of 4 waves per CU
-    if (!mixed) return launch_ci16_dot2_shape<NT, BLOCK, 2, MD>(L, channels, mixed, s);
+    constexpr int BLOCK = MD == 1 ? 256 : 512;
+    if (!mixed) return launch_ci16_dot2_shape<NT, BLOCK, 0, MD>(L, channels, mixed, s);
     const unsigned pe = mixer_seq_period(L.mix_N, L.mix_freq);
     if (pe > kSeqMax) return launch_ci16_dot2_shape<NT, BLOCK, 1, MD>(L, channels, mixed, s);
     // two-word sequence tables: stored twice up to Pe = 2048, once (index
@@ -234,7 +222,6 @@ int launch_generic(const DecimLaunch &L, int channels, unsigned M, bool fma, hip
     return SRCDSP_OK;
 }
 
-bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
 bool aligned8(const void *p) { return ((uintptr_t)p & 7u) == 0; }
 }  // namespace
 
@@ -482,22 +469,16 @@ static int core_step(FirCore &f, const void *d_in, size_t n_in, void *d_out, siz
     L.shift = f.shift();
     L.hist_in[0] = f.d_hist[f.cur];
     L.hist_out[0] = f.d_hist[f.cur ^ 1];
-    if (mix) {
+    if (mix) {  // what the handles hold; the launcher adds its kernel's tile phases
         const unsigned long N = mix->N, fr = (unsigned)mix->freq, phi0 = (unsigned)mix->phi;
-        // phase of sample i: (phi0 + i*fr) mod N, for any sign of i
-        auto phase = [&](long i) {
-            long m = i % (long)N;
-            if (m < 0) m += (long)N;
-            return (unsigned)((phi0 + (unsigned long)m * fr) % N);
-        };
-        constexpr long kNQ = 32;  // taps 127/128: ceil(N/4) polyphase steps
         L.mix_table = mix->d_table;
         L.mix_N = mix->N;
         L.mix_phase0 = (unsigned)phi0;
         L.mix_freq = (unsigned)fr;
-        L.mix_phase_tile0 = phase(-4 * kNQ);
-        L.mix_dtile = phase_step(N, fr, 4ul * kCiBlock_ * kCiR_);  // reset per kernel tile
-        L.mix_phase_hist = phase((long)n_in - (f.ntaps - 1));
+        // phase of sample n_in - H: (phi0 + i*fr) mod N, for either sign of i
+        long m = ((long)n_in - (f.ntaps - 1)) % (long)N;
+        if (m < 0) m += (long)N;
+        L.mix_phase_hist = (unsigned)((phi0 + (unsigned long)m * fr) % N);
     }
     rc = decim_launch(f, L, 1, s, mix != nullptr);
     if (rc) return rc;
@@ -524,6 +505,43 @@ static int core_step_host(FirCore &f, const void *in, size_t n_in, void *out, si
     return SRCDSP_OK;
 }
 
+// create / clone of a handle H = {FirCore core;} (srcdsp_decim, srcdsp_fir):
+// *out is the new handle, or null when its core could not be set up
+template <typename H>
+static int handle_create(H **out, int kv, unsigned M, const void *coeffs, int ntaps, unsigned flags) {
+    auto *h = new H();
+    int rc = h->core.init(kv, M, coeffs, ntaps, flags);
+    if (rc) {
+        h->core.destroy();
+        delete h;
+        return rc;
+    }
+    *out = h;
+    return SRCDSP_OK;
+}
+
+template <typename H>
+static int handle_clone(H *h, H **out) {
+    *out = nullptr;
+    auto *c = new H();
+    int rc = c->core.clone_from(h->core);
+    if (rc) {
+        c->core.destroy();
+        delete c;
+        return rc;
+    }
+    *out = c;
+    return SRCDSP_OK;
+}
+
+template <typename H>
+static int handle_destroy(H *h) {
+    if (!h) return SRCDSP_OK;
+    h->core.destroy();
+    delete h;
+    return SRCDSP_OK;
+}
+
 }  // namespace srcdsp
 
 using namespace srcdsp;
@@ -540,36 +558,14 @@ SRCDSP_API int srcdsp_decim_create(srcdsp_decim_t *out, int variant, unsigned M,
         return SRCDSP_ERR_UNSUPPORTED;
     }
     SRCDSP_ARG_CHECK(M >= 1, "decim_create: M must be >= 1");
-    auto *h = new srcdsp_decim();
-    int rc = h->core.init(variant, M, coeffs, ntaps, flags);
-    if (rc) {
-        h->core.destroy();
-        delete h;
-        return rc;
-    }
-    *out = h;
-    return SRCDSP_OK;
+    return handle_create(out, variant, M, coeffs, ntaps, flags);
 }
 
-SRCDSP_API int srcdsp_decim_destroy(srcdsp_decim_t h) {
-    if (!h) return SRCDSP_OK;
-    h->core.destroy();
-    delete h;
-    return SRCDSP_OK;
-}
+SRCDSP_API int srcdsp_decim_destroy(srcdsp_decim_t h) { return handle_destroy(h); }
 
 SRCDSP_API int srcdsp_decim_clone(srcdsp_decim_t h, srcdsp_decim_t *out) {
     SRCDSP_ARG_CHECK(h != nullptr && out != nullptr, "decim_clone: null argument");
-    *out = nullptr;
-    auto *c = new srcdsp_decim();
-    int rc = c->core.clone_from(h->core);
-    if (rc) {
-        c->core.destroy();
-        delete c;
-        return rc;
-    }
-    *out = c;
-    return SRCDSP_OK;
+    return handle_clone(h, out);
 }
 
 SRCDSP_API int srcdsp_decim_set_coeffs(srcdsp_decim_t h, const void *coeffs, int ntaps, int require_multiple) {
@@ -683,36 +679,14 @@ SRCDSP_API int srcdsp_fir_create(srcdsp_fir_t *out, int variant, const void *coe
         set_error("fir_create: variant must be 0..2");
         return SRCDSP_ERR_UNSUPPORTED;
     }
-    auto *h = new srcdsp_fir();
-    int rc = h->core.init(kFirKV[variant], 1, coeffs, ntaps, flags);
-    if (rc) {
-        h->core.destroy();
-        delete h;
-        return rc;
-    }
-    *out = h;
-    return SRCDSP_OK;
+    return handle_create(out, kFirKV[variant], 1, coeffs, ntaps, flags);
 }
 
-SRCDSP_API int srcdsp_fir_destroy(srcdsp_fir_t h) {
-    if (!h) return SRCDSP_OK;
-    h->core.destroy();
-    delete h;
-    return SRCDSP_OK;
-}
+SRCDSP_API int srcdsp_fir_destroy(srcdsp_fir_t h) { return handle_destroy(h); }
 
 SRCDSP_API int srcdsp_fir_clone(srcdsp_fir_t h, srcdsp_fir_t *out) {
     SRCDSP_ARG_CHECK(h != nullptr && out != nullptr, "fir_clone: null argument");
-    *out = nullptr;
-    auto *c = new srcdsp_fir();
-    int rc = c->core.clone_from(h->core);
-    if (rc) {
-        c->core.destroy();
-        delete c;
-        return rc;
-    }
-    *out = c;
-    return SRCDSP_OK;
+    return handle_clone(h, out);
 }
 
 // setCoeffs (filters.h:86-97) ends in reset(): the buffer is cleared.

@@ -59,13 +59,15 @@ struct DecimLaunch {
     const int16_t *mix_table;
     unsigned mix_N;
     unsigned mix_phase0, mix_freq;
-    // host-precomputed phases (no 64-bit modulo on the device):
-    unsigned mix_phase_tile0;  // phase of tile 0's first staged sample (index -4*NQ)
-    unsigned mix_dtile;        // phase advance per tile (4*TO samples)
+    // host-precomputed phases (no 64-bit modulo on the device).  The first
+    // two depend on the kernel's geometry and are set by its launcher:
+    unsigned mix_phase_tile0;  // phase of tile 0's first staged sample (index -halo)
+    unsigned mix_dtile;        // phase advance per tile (its input samples)
     unsigned mix_phase_hist;   // phase of input sample n_in - H (history write-back)
-    // sequence-table mixer (decim_dot2_ci16 TABM = 2): the table holds the
-    // (cos, sin) word of input sample s at s mod mix_pe, mix_pe = lcm(period of
+    // sequence-table mixer (decim_dot2_ci16 TABM = 3, 4, 5): the tables hold the
+    // (cos, sin) words of input sample s at s mod mix_pe, mix_pe = lcm(period of
     // s*freq mod N, 4); per-tile / per-granule-row advances of that index
+    // (forms 3 and 4; form 5 keeps its words in registers)
     unsigned mix_pe, mix_pe_dtile, mix_pe_drow;
     const void *hist_in[kMaxBatch];
     void *hist_out[kMaxBatch];
@@ -75,6 +77,7 @@ int decim_launch(FirCore &f, const DecimLaunch &L, int channels, hipStream_t s, 
 // the complex<float> headline kernel (decim_cf32_ct.hip / decim_cf32_rt.hip):
 // with the tap count compiled in (SRCDSP_ERR_UNSUPPORTED for a shape it is not
 // compiled for), or at run time (M in 1/2/3/4/8/16, N <= kCfMaxTaps)
+constexpr int kCfMaxTaps = 1024;
 int launch_cf32_compiled(DecimLaunch L, int channels, unsigned M, int N, bool fma, hipStream_t s);
 int launch_cf32_rt(DecimLaunch L, int channels, unsigned M, bool fma, hipStream_t s);
 

@@ -368,6 +368,37 @@ def test_mixdecim_chain_table_sizes(S, O, N, f):
         assert m.state()[:2] == om.state()[:2]
 
 
+@pytest.mark.parametrize("kind,ntaps", [("i16", 127), ("i16", 128), ("i24", 127), ("i24", 128)])
+def test_mixdecim_chain_compiled_taps_tile_phases(S, O, kind, ntaps):
+    """The fused mixer's per-tile phases in the two kernels with the tap count
+    compiled in: int16-range taps (the v_dot2 kernel, tiles of 8192 input
+    samples) and taps beyond it with |c| < 2^23 (the v_mad_i32_i24 kernel,
+    tiles of 4096), 127 and 128 taps.  Two consecutive steps of three whole
+    tiles and a part of a fourth, with a mixer whose phase wraps on no power
+    of two: outputs, mixer phase and decimator history (the last ntaps - 1
+    mixed samples) bit for bit those of the two reference calls."""
+    from srcdsp_amd.design import hamming_sinc, q14
+    cq = q14(hamming_sinc(ntaps))
+    span = 8192
+    if kind == "i24":
+        cq = cq.astype(np.int32) * 64  # |c| < 2^23, beyond int16
+        span = 4096
+    n = 3 * span + 4 * 5
+    x = O["strict"].gen_ci16(0x71E + ntaps, 3, 0, 2 * n, -32768, 32767)
+    m = S.Mixer(1000)
+    m.reset(-0.37)
+    d = S.FilterDnsamplingFir(cq, 4, "complex<int16_t>", "complex<int16_t>", "complex<int32_t>", "int32_t")
+    chain = S.MixerDecimatorChain(m, d)
+    om, od = O["strict"].mixer(1000), O["strict"].decim(1, 4, cq)
+    om.reset(-0.37)
+    for off in (0, n):
+        xs = x[off:off + n]
+        mixed = om.step(xs)
+        assert np.array_equal(chain.step(dev(xs)).cpu().numpy(), od.step(mixed)), off
+        assert m.state()[:2] == om.state()[:2]
+        assert d.state()["history"].tobytes() == np.ascontiguousarray(mixed[n - (ntaps - 1):]).tobytes(), off
+
+
 @pytest.mark.parametrize("case", ["m3", "t63_i24", "t16taps", "wide_taps", "n8192", "out_offset", "in_offset"])
 def test_mixdecim_chain_unfused_configs(S, O, case):
     """Chain configurations the fused kernels do not cover run as the two
