@@ -233,6 +233,27 @@ SRCDSP_API int srcdsp_corr_step_host(srcdsp_corr_t h, const void *in, size_t n, 
  * (correlators.h:221-250 without :262-291): history ring and the
  * energy/correlation registers.  Seeds a time segment with its halo. */
 SRCDSP_API int srcdsp_corr_prime(srcdsp_corr_t h, const void *d_in, size_t n, void *stream);
+/* Extension (no reference call).  C correlators stepped in one call: for every
+ * channel c exactly hs[c].step(in_c, corrIndex_c) (correlators.h:209-303),
+ * in_c = d_in + c*in_stride samples of complex<int16_t>, n samples each.
+ * in_stride == 0: every channel scans the SAME n samples (several sync words
+ * searched in one stream).  found[c] = 0/1 and corr_index[c] (written only
+ * when found) are host arrays of `channels` entries.  Channels are
+ * independent: each scans up to its own first detection.  Every handle is left
+ * as srcdsp_corr_step leaves it (registers, history, bitSamples, stream
+ * ordering).  Synchronous, with at most two host synchronisations per call
+ * whatever `channels` is.
+ * The handles must share N and S (patterns and scalings may differ) and be
+ * listed once each; channels >= 1 (SRCDSP_ERR_ARG otherwise).  n == 0 is OK
+ * with every found[c] = 0; n > INT_MAX is SRCDSP_ERR_SIZE.  A refused call
+ * changes no handle.
+ * One bank kernel serves S == 1 with int16-range patterns and N <= 8192 (the
+ * shapes of the fused single-channel scan); every other shape runs
+ * srcdsp_corr_step per channel inside the call. */
+SRCDSP_API int srcdsp_corr_step_batched(const srcdsp_corr_t *hs, int channels, const void *d_in, size_t in_stride,
+                                        size_t n, int *found, int *corr_index, void *stream);
+/* process-wide counters: calls served by the bank kernel, calls served by the per-channel loop */
+SRCDSP_API int srcdsp_corr_batched_stats(unsigned long *bank_calls, unsigned long *loop_calls);
 /* step() as built with CREATE_DEBUG_FILES (correlators.h:107-132, 253-257):
  * also returns, for every sample the call processed, the registers the
  * reference writes to its debug files -- corr_out[k] = corrValue[0] and

@@ -128,7 +128,7 @@ int launch_cf32(""")
 
 # the correlator's fused scan on the i8 matrix cores (scripts/tune/corr_mfma_scan.h)
 PATCHES["corrmfma"] = [
-    ("corr.hip", "    unsigned *d_best = nullptr;\n",
+    ("corr_state.h", "    unsigned *d_best = nullptr;\n",
      "    unsigned *d_best = nullptr;\n"
      "    int mfma_pl = 0;             // tuning variant: 1 or 2 pattern limbs, 0 = the product path\n"
      "    uint32_t mfma_scale = 1, mfma_bias[2] = {0u, 0u};\n"
@@ -154,7 +154,7 @@ PATCHES["corrmfma"] = [
     ("corr.hip", "    c.cur = 0;\n    *out = n;\n",
      "    c.cur = 0;\n    rc = corr_mfma_prepare(c);\n    if (rc) {\n        srcdsp_corr_destroy(n);\n"
      "        return rc;\n    }\n    *out = n;\n"),
-    ("corr.hip", "(void *)c.d_best})", "(void *)c.d_best, (void *)c.d_mfma_b, (void *)c.d_seams})"),
+    ("corr.hip", "(void *)c.d_bank})", "(void *)c.d_bank, (void *)c.d_mfma_b, (void *)c.d_seams})"),
 ]
 
 # variants whose patch sites the product sources have since moved past (the

@@ -14,6 +14,8 @@ from .operators import (  # noqa: F401
     FixedPatternCorrelator,
     Mixer,
     MixerDecimatorChain,
+    corr_batched_stats,
+    corr_step_batched,
     decim_step_batched,
     fill_synthetic,
     mixdecim_batched_stats,
@@ -22,4 +24,4 @@ from .operators import (  # noqa: F401
 
 __all__ = ["FifoWithTimeTrack", "files", "FilterDnsamplingFir", "FilterFir", "FilterUpsamplingFir", "Mixer", "MixerDecimatorChain",
            "FixedPatternCorrelator", "decim_step_batched", "mixdecim_step_batched", "mixdecim_batched_stats",
-           "fill_synthetic", "SrcdspError", "lib"]
+           "corr_step_batched", "corr_batched_stats", "fill_synthetic", "SrcdspError", "lib"]

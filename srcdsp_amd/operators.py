@@ -504,6 +504,39 @@ class FixedPatternCorrelator(_Handle):
     status = getStatus
 
 
+def corr_step_batched(correlators, inp):
+    """Step C correlators in one call: channel c is exactly
+    ``correlators[c].step(inp_c)``, each scanning up to its own first
+    detection.  ``inp`` is a device tensor of complex<int16_t> samples: int16
+    [n, 2], one input every channel scans (several patterns searched in one
+    stream), or [C, n, 2], one contiguous row per channel.  The correlators
+    share N and S; patterns may differ.  Returns a list of (found, corrIndex),
+    corrIndex meaningful only if found."""
+    ch = len(correlators)
+    if ch < 1:
+        raise ValueError("corr_step_batched: at least one correlator")
+    if not _is_device(inp):
+        raise TypeError("corr_step_batched() takes a device-resident buffer")
+    if inp.dim() not in (2, 3) or inp.shape[-1] != 2 or inp.element_size() != 2:
+        raise ValueError("corr_step_batched: inp is int16 [n, 2] (shared) or [C, n, 2]")
+    shared = inp.dim() == 2
+    if not shared and inp.shape[0] != ch:
+        raise ValueError("corr_step_batched: one input row per correlator")
+    n = inp.shape[-2]
+    hs = (C.c_void_p * ch)(*[c._h.value for c in correlators])
+    found, idx = (C.c_int * ch)(), (C.c_int * ch)(*([-1] * ch))
+    A.call("srcdsp_corr_step_batched", hs, ch, _ptr(inp), 0 if shared else n, n, found, idx, _stream(inp))
+    return [(bool(found[c]), idx[c]) for c in range(ch)]
+
+
+def corr_batched_stats():
+    """(bank_calls, loop_calls): batched correlator calls served by the bank
+    kernel and by the per-channel loop, process-wide."""
+    b, l = C.c_ulong(), C.c_ulong()
+    A.call("srcdsp_corr_batched_stats", C.byref(b), C.byref(l))
+    return b.value, l.value
+
+
 def fill_synthetic(t, kind: str, seed: int = 0x5EED, channel: int = 0, offset: int = 0, lo: int = -2048,
                    hi: int = 2047):
     """Fill a device tensor with the counter-based synthetic samples."""
