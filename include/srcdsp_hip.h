@@ -205,6 +205,44 @@ SRCDSP_API int srcdsp_mixdecim_step_batched(const srcdsp_mixer_t *mixers, const 
 /* process-wide counters: calls served by the bank kernel, calls served by the per-channel loop */
 SRCDSP_API int srcdsp_mixdecim_batched_stats(unsigned long *bank_calls, unsigned long *loop_calls);
 
+/* FilterUpsamplingFir (variant 0 or 1) -> Mixer fused, the transmit chain: the
+ * two reference calls up.step(in, tmp, flush) (upsampling_filters.h:149-233;
+ * iterator=1: the iterator overload's shift 0, :240-323); mixer.step(tmp, out)
+ * (mixers.h:169-188) in one pass with no intermediate buffer.  Every output is
+ * limitScale16(limitScale<complex<int16_t>>(y, shift) * lo, 14): the
+ * interpolator's asymmetric clamp to int16 (dsp_complex.h:83-108), then the
+ * mixer's product and symmetric clamp (dsp_complex.cpp:31-37, 63-73).
+ * n_out must be exactly L*n_in, or L*(n_in + length/L) when flush
+ * (SRCDSP_ERR_SIZE otherwise; unlike srcdsp_up_step no larger buffer when
+ * flushing: the mixer would step over the slack).  The mixer advances by n_out
+ * samples, flushed ones included, the interpolator's history as in
+ * srcdsp_up_step; a later single-operator call on either handle continues bit
+ * for bit.  Variant 2 (real int16_t) cannot feed the mixer:
+ * SRCDSP_ERR_UNSUPPORTED.  A refused call changes no handle.
+ * One kernel serves variant 0 with int16-range taps, L = 2..8, <= 4096 taps,
+ * 16-byte aligned d_in and d_out and a mixer of N <= 4096; every other shape
+ * runs srcdsp_up_step into d_out and srcdsp_mixer_step in place on it. */
+SRCDSP_API int srcdsp_upmix_step(srcdsp_up_t up, srcdsp_mixer_t mixer, const void *d_in, size_t n_in,
+                                 void *d_out, size_t n_out, int flush, int iterator, void *stream);
+/* Extension (no reference call).  C such chains in one call (vector overload):
+ * channel c reads d_in + c*in_stride samples and writes the row d_out +
+ * c*out_stride samples exactly as srcdsp_upmix_step(ups[c], mixers[c], ...)
+ * would.  in_stride == 0: every channel reads the SAME n_in samples (one
+ * baseband stream onto C carriers); otherwise in_stride >= n_in.  out_stride >=
+ * L*(n_in + length/L when flush) (SRCDSP_ERR_SIZE otherwise); samples of a row
+ * past that are not written.  The interpolators must share variant, L and
+ * taps, the mixers N; every handle is listed once; channels >= 1
+ * (SRCDSP_ERR_ARG otherwise).  One launch (grid.y = channel) serves the shapes
+ * the single call's kernel serves when the row strides are multiples of 16
+ * bytes too; every other shape runs the single call per channel. */
+SRCDSP_API int srcdsp_upmix_step_batched(const srcdsp_up_t *ups, const srcdsp_mixer_t *mixers, int channels,
+                                         const void *d_in, size_t in_stride, void *d_out, size_t out_stride,
+                                         size_t n_in, int flush, void *stream);
+/* process-wide counters: single calls served by the fused kernel / by the pair
+ * of operators, batched calls served by one launch / by the per-channel loop */
+SRCDSP_API int srcdsp_upmix_stats(unsigned long *fused_calls, unsigned long *pair_calls,
+                                  unsigned long *bank_calls, unsigned long *loop_calls);
+
 /* ============================================================================
  * FixedPatternCorrelator<int16_t, int32_t, N, S>   (correlators.h:54-316)
  * ==========================================================================*/

@@ -20,8 +20,12 @@ from .operators import (  # noqa: F401
     fill_synthetic,
     mixdecim_batched_stats,
     mixdecim_step_batched,
+    UpsamplerMixerChain,
+    upmix_stats,
+    upmix_step_batched,
 )
 
 __all__ = ["FifoWithTimeTrack", "files", "FilterDnsamplingFir", "FilterFir", "FilterUpsamplingFir", "Mixer", "MixerDecimatorChain",
+           "UpsamplerMixerChain", "upmix_step_batched", "upmix_stats",
            "FixedPatternCorrelator", "decim_step_batched", "mixdecim_step_batched", "mixdecim_batched_stats",
            "corr_step_batched", "corr_batched_stats", "fill_synthetic", "SrcdspError", "lib"]

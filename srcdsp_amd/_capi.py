@@ -63,6 +63,9 @@ SIGNATURES = {
     "srcdsp_mixdecim_step": (I, [VP, VP, VP, SZ, VP, SZ, VP]),
     "srcdsp_mixdecim_step_batched": (I, [HP, HP, I, VP, SZ, VP, SZ, SZ, VP]),
     "srcdsp_mixdecim_batched_stats": (I, [C.POINTER(C.c_ulong), C.POINTER(C.c_ulong)]),
+    "srcdsp_upmix_step": (I, [VP, VP, VP, SZ, VP, SZ, I, I, VP]),
+    "srcdsp_upmix_step_batched": (I, [HP, HP, I, VP, SZ, VP, SZ, SZ, I, VP]),
+    "srcdsp_upmix_stats": (I, [C.POINTER(C.c_ulong)] * 4),
     "srcdsp_corr_create": (I, [HP, U, U]),
     "srcdsp_corr_destroy": (I, [VP]),
     "srcdsp_corr_clone": (I, [VP, HP]),

@@ -1,0 +1,318 @@
+// up_dot2_kernels.h -- the interpolator's handle layout and its v_dot2 tile
+// (FilterUpsamplingFir, upsampling_filters.h:36-326), shared by upsamp.hip
+// (srcdsp_up_step) and upmix.hip (the interpolator -> mixer chain, which runs
+// the same tile with the mixer in its output epilogue).
+#pragma once
+#include <string>
+
+#include "ops.h"
+
+namespace srcdsp {
+
+enum { UV_CI16_I32 = 0, UV_CI16_I16 = 1, UV_I16_I32 = 2 };
+typedef short short2_t_u __attribute__((ext_vector_type(2)));
+
+struct srcdsp_up_state {
+    int variant = 0;
+    unsigned L = 1;
+    int ntaps = 0, H = 0;
+    unsigned length = 0;
+    int left_shift_factor = 0;
+    std::string h_raw;          // the taps as given (CoefType bytes), for copies
+    int32_t *d_coef = nullptr;  // polyphase order: d_coef[o*H + i] = c[o + i*L]
+    bool coef_i24 = false;      // every tap in (-2^23, 2^23): v_mad_i32_i24
+    bool coef_i16 = false;      // every tap in int16 range: v_dot2 tap pairs (variant 0)
+    uint32_t *d_pair = nullptr; // per phase o: pairs[o*(H/2+1) + p] = (lo c_o[2p], hi c_o[2p-1])
+    void *d_hist[2] = {nullptr, nullptr};
+    size_t hist_cap = 0;
+    int cur = 0;
+    Ordering order;
+    HostStage stage;
+};
+
+// sample j of the virtual stream (history ++ input ++ flush zeros), as a packed word
+template <int UV>
+__device__ __forceinline__ uint32_t up_fetch(const void *in, const void *hist, long j, long n_in, int Hm1) {
+    if (j < 0) {
+        long h = j + Hm1;
+        if (h < 0) return 0;
+        return UV == UV_I16_I32 ? (uint32_t)(uint16_t)((const int16_t *)hist)[h] : ((const uint32_t *)hist)[h];
+    }
+    if (j >= n_in) return 0;
+    return UV == UV_I16_I32 ? (uint32_t)(uint16_t)((const int16_t *)in)[j] : ((const uint32_t *)in)[j];
+}
+
+constexpr int kUpMaxTaps = 4096;
+
+// Tiled polyphase interpolator on v_dot2_i32_i16 (variant 0 with int16-range
+// taps, LR in 2..8).  Each lane owns RD = 8 consecutive input samples.  Taps
+// of phase o are paired Q_p = (lo c_o[2p+1], hi c_o[2p]) (c_o[H] = 0), p <
+// ceil(H/2); the pair of input j multiplies the packed samples (x[j-2p-1],
+// x[j-2p]), which for even j = 2m is dword m-p-1 of an odd-aligned plane
+// O[e] = (x[2e+1], x[2e+2]) and for odd j = 2m+1 dword m-p of an even-aligned
+// plane E[e] = (x[2e], x[2e+1]).  A lane's 8 inputs read O[4t'+r/2-1-p] (even
+// r) / E[4t'+(r-1)/2-p] (odd r): one 4-dword register window per plane and
+// component sliding one dword per pair, one ds_read_b128 per plane every 4
+// pairs.  ceil(H/2) dot2 per phase and component (the (c[2p], c[2p-1])
+// pairing needed H/2 + 1).  int16 x int16 -> int32 products, wrap-around
+// accumulate: exactly the reference's complex<int32_t> arithmetic.
+constexpr int kUpRD = 8, kUpBlockD = 256;
+
+// dynamic LDS of one tile: the four input planes, reused for the staged output
+inline size_t up_dot2_smem(int H, unsigned L) {
+    const int PP = (H + 1) / 2, HG = (PP + 3) / 4, PGR = kUpRD * kUpBlockD / 8 + HG;
+    const size_t out_lds = 16 * (size_t)kUpBlockD * (kUpRD * L / 4 + 1);  // staged output tile
+    return 4 * 16 * (size_t)PGR > out_lds ? 4 * 16 * (size_t)PGR : out_lds;
+}
+
+// the interpolator alone: every packed output word is stored as it is
+struct UpStoreEpilogue {
+    __device__ __forceinline__ void begin(int) {}
+    __device__ __forceinline__ uint32_t operator()(uint32_t w) { return w; }
+};
+
+// One tile (blockIdx.x) of the call.
+// WS: window register sets (3: the next granule is read a chunk ahead, 150
+// VGPRs at LR = 4; 2: it is read at the end of the chunk into the set that
+// chunk is done with, <= 128 VGPRs -> 4 waves per SIMD)
+// PPC: pairs per phase as a compile-time constant (0: runtime, from H): the
+// chunk loop unrolls completely, the window sets rotate without register
+// copies and each accumulator starts with a dot2 into an inline 0.
+// EPI: what happens to a lane's 8 LR packed output words on their way to the
+// output tile: epi.begin(k) with k the lane's first output word within the
+// tile, then epi(word) once per word in output order.
+template <int LR, bool NTS, int WS, int PPC, class EPI>
+__device__ __forceinline__ void up_dot2_tile(const uint32_t *in, long n_in, long n_total, const uint32_t *hist_in,
+                                             uint32_t *hist_out, const uint32_t *pairs, int H, unsigned shift,
+                                             uint32_t *out, EPI &epi) {
+    constexpr int R = kUpRD, TI = R * kUpBlockD;
+    extern __shared__ uint4 ug[];  // 4 planes (E_re, E_im, O_re, O_im) of PGR granules each
+    const int Hm1 = H - 1;
+    const int PP = PPC ? PPC : (H + 1) / 2;  // pairs per phase
+    const int HG = (PP + 3) / 4;         // halo granules per plane (window reach: dword D0 - PP)
+    const int PGR = TI / 8 + HG;         // granules per plane (4 dwords = 8 samples)
+    const int t = threadIdx.x;
+    if (blockIdx.x == 0) {
+        for (int k = t; k < Hm1; k += kUpBlockD) {
+            const long j = n_total - Hm1 + k;
+            hist_out[k] = up_fetch<UV_CI16_I32>(in, hist_in, j, n_in, Hm1);
+        }
+    }
+    const long j0 = (long)blockIdx.x * TI;
+    // staging: sample granule g (4 samples from j0 - 8*HG + 4g) -> plane dwords 2g, 2g+1
+    uint32_t *pl = (uint32_t *)ug;
+    const int PDW = 4 * PGR;  // dwords per plane
+    const int ng = 2 * PGR;
+    auto lo = [](uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x05040100u); };
+    auto hi = [](uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x07060302u); };
+    auto put = [&](int g, const uint32_t (&w)[5]) {
+        *(uint2 *)&pl[0 * PDW + 2 * g] = make_uint2(lo(w[0], w[1]), lo(w[2], w[3]));
+        *(uint2 *)&pl[1 * PDW + 2 * g] = make_uint2(hi(w[0], w[1]), hi(w[2], w[3]));
+        *(uint2 *)&pl[2 * PDW + 2 * g] = make_uint2(lo(w[1], w[2]), lo(w[3], w[4]));
+        *(uint2 *)&pl[3 * PDW + 2 * g] = make_uint2(hi(w[1], w[2]), hi(w[3], w[4]));
+    };
+    // a tile whose whole span (halo included) lies inside the input: the
+    // lane's first three granules are loaded together, then written (one
+    // exposed load latency per tile instead of one per granule)
+    constexpr int NI = 3;
+    const bool interior = j0 - 8L * HG >= 0 && j0 + TI + 1 <= n_in;
+    int g1 = t;  // first granule of the generic loop
+    if (interior) {
+        uint32_t w[NI][5];
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            const int g = t + i * kUpBlockD;
+            if (i < 2 || g < ng) {  // ng >= 2 * kUpBlockD
+                const long s0 = j0 - 8L * HG + 4L * g;
+                const uint4 v = *(const uint4 *)(in + s0);
+                w[i][0] = v.x; w[i][1] = v.y; w[i][2] = v.z; w[i][3] = v.w;
+                w[i][4] = in[s0 + 4];
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < NI; ++i)
+            if (i < 2 || t + i * kUpBlockD < ng) put(t + i * kUpBlockD, w[i]);
+        g1 = t + NI * kUpBlockD;
+    }
+    for (int g = g1; g < ng; g += kUpBlockD) {
+        const long s0 = j0 - 8L * HG + 4L * g;
+        uint32_t w[5];
+        if (s0 >= 0 && s0 + 5 <= n_in) {
+            const uint4 v = *(const uint4 *)(in + s0);
+            w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+            w[4] = in[s0 + 4];
+        } else {
+#pragma unroll
+            for (int k = 0; k < 5; ++k) w[k] = up_fetch<UV_CI16_I32>(in, hist_in, s0 + k, n_in, Hm1);
+        }
+        put(g, w);
+    }
+    __syncthreads();
+    // lane base: input j0 + 8t = plane dword D0 = 4t + 4*HG (granule gb).  Input
+    // r, pair p reads dword D0 + k - p, k = r/2 - 1 in plane O for even r,
+    // k = (r-1)/2 in plane E for odd r:
+    // for the chunk of pairs 4q..4q+3 those are dwords of granules gb - q
+    // (`cur`) and gb - q - 1 (`nxt`), two register sets that swap roles.
+    const int gb = t + HG;
+    int32_t yr[LR][R], yi[LR][R];
+    if constexpr (PPC == 0) {
+#pragma unroll
+        for (int o = 0; o < LR; ++o)
+#pragma unroll
+            for (int r = 0; r < R; ++r) yr[o][r] = yi[o][r] = 0;
+    }
+    ConstPtr<uint32_t> tp = const_view<uint32_t>(pairs);
+    // Three window register sets rotate over the chunks and the taps of a
+    // chunk (4 pairs x LR phases, contiguous: dword (4q + pp) LR + o) arrive in
+    // one s_load; both for chunk q+1 are requested after chunk q's first pair,
+    // so the lgkmcnt wait at chunk q+1 lands three pairs of dot2 after them
+    // (waiting on a tap s_load drains every LDS read in flight too).
+    uint32_t W0[4][4], W1[4][4], W2[4][4];  // [plane][dword]
+    constexpr int TPC = 4 * LR;            // tap dwords per chunk
+    uint32_t Tc[TPC], Tn[TPC];
+    auto load = [&](uint32_t (&w)[4][4], int gi) {
+#pragma unroll
+        for (int pl4 = 0; pl4 < 4; ++pl4) {
+            typedef uint32_t u4v_t __attribute__((ext_vector_type(4)));
+            // volatile keeps every window read a whole ds_read_b128
+            // (conflict-free at the lanes' 16-B stride): at the window's far end
+            // the compiler would read only the dwords used, as ds_read_b32 /
+            // ds_read2_b32, whose 32-lane groups at a 16-B stride hit 8 banks
+            typedef const volatile __attribute__((address_space(3))) u4v_t *lds_u4v;
+            const u4v_t v = *(lds_u4v)(&ug[pl4 * PGR + gi]);
+            w[pl4][0] = v[0]; w[pl4][1] = v[1]; w[pl4][2] = v[2]; w[pl4][3] = v[3];
+        }
+    };
+    auto load_taps = [&](uint32_t (&T)[TPC], int q) {
+        asm volatile("" : "+s"(tp));
+#pragma unroll
+        for (int i = 0; i < TPC; ++i) T[i] = tp[q * TPC + i];
+    };
+    const int NQ = (PP + 3) / 4;
+    auto chunk = [&](int q, const uint32_t (&cur)[4][4], const uint32_t (&nxt)[4][4], uint32_t (&nn)[4][4]) {
+#pragma unroll
+        for (int pp = 0; pp < 4; ++pp) {
+            const int p = 4 * q + pp;
+            if (p >= PP) break;  // the last chunk only
+            if (WS == 3 && pp == 1 && q + 1 < NQ) {
+                load(nn, gb - q - 2);
+                load_taps(Tn, q + 1);
+            }
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const int k = (r & 1) ? (r >> 1) : (r >> 1) - 1, rel = k - pp;  // -4..3
+                const int pr = (r & 1) ? 0 : 2, pi = pr + 1;  // planes E_re/E_im or O_re/O_im
+                const uint32_t xr = rel >= 0 ? cur[pr][rel] : nxt[pr][rel + 4];
+                const uint32_t xi = rel >= 0 ? cur[pi][rel] : nxt[pi][rel + 4];
+#pragma unroll
+                for (int o = 0; o < LR; ++o) {
+                    const uint32_t P = Tc[pp * LR + o];
+                    if (PPC && q == 0 && pp == 0) {  // first pair: into an inline 0
+                        asm("v_dot2_i32_i16 %0, %1, %2, 0" : "=v"(yr[o][r]) : "v"(xr), "s"(P));
+                        asm("v_dot2_i32_i16 %0, %1, %2, 0" : "=v"(yi[o][r]) : "v"(xi), "s"(P));
+                    } else {
+                        yr[o][r] = __builtin_amdgcn_sdot2(__builtin_bit_cast(short2_t_u, xr),
+                                                          __builtin_bit_cast(short2_t_u, P), yr[o][r], false);
+                        yi[o][r] = __builtin_amdgcn_sdot2(__builtin_bit_cast(short2_t_u, xi),
+                                                          __builtin_bit_cast(short2_t_u, P), yi[o][r], false);
+                    }
+                }
+            }
+        }
+        if constexpr (WS == 3) {
+#pragma unroll
+            for (int i = 0; i < TPC; ++i) Tc[i] = Tn[i];
+        }
+    };
+    load(W0, gb);
+    load(W1, gb - 1);
+    load_taps(Tc, 0);
+    int q = 0;
+    if constexpr (WS == 3) {
+#pragma unroll
+        for (; q + 3 <= NQ; q += 3) {
+            chunk(q, W0, W1, W2);
+            chunk(q + 1, W1, W2, W0);
+            chunk(q + 2, W2, W0, W1);
+        }
+        if (q < NQ) chunk(q, W0, W1, W2);
+        if (q + 1 < NQ) chunk(q + 1, W1, W2, W0);
+    } else {
+        // chunk q reads granules gb-q (cur) and gb-q-1 (nxt); the next chunk's
+        // new granule gb-q-2 goes into cur once this chunk is done with it
+        (void)W2;
+        auto chunk2 = [&](int qq, uint32_t (&cur)[4][4], const uint32_t (&nxt)[4][4]) {
+            uint32_t none[4][4];
+            chunk(qq, cur, nxt, none);  // no early read (nn unused when WS == 2)
+            if (qq + 1 < NQ) {
+                load(cur, gb - qq - 2);
+                load_taps(Tc, qq + 1);
+            }
+        };
+#pragma unroll
+        for (; q + 2 <= NQ; q += 2) {
+            chunk2(q, W0, W1);
+            chunk2(q + 1, W1, W0);
+        }
+        if (q < NQ) chunk2(q, W0, W1);
+    }
+    // outputs -> LDS (lane chunk of 8*LR words at a 9-granule stride for LR = 4,
+    // conflict-free) -> whole-line 16-B stores of the tile's contiguous output
+    constexpr int GPLo = R * LR / 4;    // output granules per lane
+    constexpr int STR = GPLo + 1;       // padded lane stride (odd)
+    // (each lane storing its own 128-B output line directly, 8 x 16 B at a
+    // 128-B lane stride, measured 30 % slower with plain stores and 5.5x
+    // slower with nt stores than this LDS transpose into whole-line stores:
+    // profiles/tuning/r03_up_stage_ab.txt)
+    __syncthreads();                    // every wave is done reading the planes
+    uint4 *ob = ug;
+    epi.begin(R * LR * t);
+#pragma unroll
+    for (int k = 0; k < GPLo; ++k) {
+        uint32_t w4[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int idx = 4 * k + u, r = idx / LR, o = idx % LR;
+            w4[u] = epi(limit_t16_pair(yr[o][r], yi[o][r], shift));
+        }
+        ob[t * STR + k] = make_uint4(w4[0], w4[1], w4[2], w4[3]);
+    }
+    __syncthreads();
+    const long wbase = (long)LR * j0;             // first output word of the tile
+    const long wend = (long)LR * n_total;         // output words of the call
+    // one whole ds_read_b128 per granule (volatile: the compiler split these
+    // reads into ds_read_b32 / ds_read2_b32 for the partial-tile branch, whose
+    // 32-lane groups at a 16-B stride hit 8 banks: 25 M conflict cycles per
+    // launch at L = 4, 2^26 inputs)
+    typedef uint32_t o4v_t __attribute__((ext_vector_type(4)));
+    typedef const volatile __attribute__((address_space(3))) o4v_t *lds_o4v;
+    auto oread = [&](int G) { return *(lds_o4v)(&ob[(G / GPLo) * STR + (G % GPLo)]); };
+    if (wbase + 4L * GPLo * kUpBlockD <= wend) {
+        // whole tile: every granule read, then every store issued, at one
+        // base address (no per-store range checks)
+        o4v_t v[GPLo];
+#pragma unroll
+        for (int i = 0; i < GPLo; ++i) v[i] = oread(i * kUpBlockD + t);
+        uint32_t *o = out + wbase + 4L * t;
+#pragma unroll
+        for (int i = 0; i < GPLo; ++i) {
+            if constexpr (NTS) {  // streaming store: the output is written once, 4L x the input bytes
+                __builtin_nontemporal_store(v[i], (o4v_t *)(o + 4 * i * kUpBlockD));
+            } else {
+                *(o4v_t *)(o + 4 * i * kUpBlockD) = v[i];
+            }
+        }
+        return;
+    }
+    for (int i = 0; i < GPLo; ++i) {  // the call's last, partial tile
+        const int G = i * kUpBlockD + t;          // output granule within the tile
+        const o4v_t vv4 = oread(G);
+        const long w0 = wbase + 4L * G;
+        for (int u = 0; u < 4; ++u)
+            if (w0 + u < wend) out[w0 + u] = vv4[u];
+    }
+}
+
+}  // namespace srcdsp
+
+struct srcdsp_up { srcdsp::srcdsp_up_state u; };

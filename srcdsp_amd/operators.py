@@ -424,6 +424,60 @@ def mixdecim_batched_stats():
     return b.value, l.value
 
 
+class UpsamplerMixerChain:
+    """up.step(in, tmp, flush); mixer.step(tmp, out) fused into one device pass
+    (the transmit chain).  Both operators' state advances exactly as the two
+    calls.  ``out`` holds exactly L*n samples (L*(n + length/L) with flush)."""
+
+    def __init__(self, up: FilterUpsamplingFir, mixer: Mixer):
+        self.up, self.mixer = up, mixer
+
+    def step(self, inp, out=None, flush: bool = False, iterator: bool = False):
+        if not _is_device(inp):
+            return self.mixer.step(self.up.step(inp, None, flush, iterator), out)
+        n = _nsamples(inp, "ci16")
+        if out is None:
+            extra = self.up.L * (self.up.getLength() // self.up.L) if flush else 0
+            out = _alloc_like(inp, "ci16", n * self.up.L + extra)
+        A.call("srcdsp_upmix_step", self.up._h, self.mixer._h, _ptr(inp), n, _ptr(out), _nsamples(out, "ci16"),
+               int(flush), int(iterator), _stream(inp))
+        return out
+
+
+def upmix_step_batched(ups, mixers, inp, out, flush: bool = False):
+    """Step C interpolator -> mixer chains in one call (a transmitter bank):
+    channel c is exactly ``UpsamplerMixerChain(ups[c], mixers[c]).step``.
+    ``inp`` of shape [n, 2] is one baseband input shared by every channel; of
+    shape [C, n, 2] one row per channel.  ``out`` is [C, >= L*(n + length/L
+    when flushing), 2]; columns past a row's samples are left untouched.
+    Device tensors of complex<int16_t> samples (int16 [..., 2])."""
+    ch = len(ups)
+    if ch < 1 or len(mixers) != ch:
+        raise ValueError("upmix bank: need one mixer per interpolator, at least one channel")
+    if not (_is_device(inp) and _is_device(out)):
+        raise ValueError("upmix bank: device tensors only")
+    if inp.dim() not in (2, 3) or inp.shape[-1] != 2 or out.dim() != 3 or out.shape[-1] != 2:
+        raise ValueError("upmix bank: inp is int16 [n, 2] (shared) or [C, n, 2], out int16 [C, L*(n + flush), 2]")
+    shared = inp.dim() == 2
+    if (not shared and inp.shape[0] != ch) or out.shape[0] != ch:
+        raise ValueError("upmix bank: one input row (or one shared input) and one output row per channel")
+    n_in = inp.shape[-2]
+    hu = (C.c_void_p * ch)(*[u._h.value for u in ups])
+    hm = (C.c_void_p * ch)(*[m._h.value for m in mixers])
+    A.call("srcdsp_upmix_step_batched", hu, hm, ch, _ptr(inp), 0 if shared else n_in, _ptr(out), out.shape[1],
+           n_in, int(flush), _stream(inp))
+    return out
+
+
+def upmix_stats():
+    """(fused_calls, pair_calls, bank_calls, loop_calls): single chain calls
+    served by the fused kernel and by the pair of operators, batched calls
+    served by one launch and by the per-channel loop, process-wide."""
+    v = [C.c_ulong() for _ in range(4)]
+    A.call("srcdsp_upmix_stats", *[C.byref(x) for x in v])
+    return tuple(x.value for x in v)
+
+
 # ======================================================== FixedPatternCorrelator
 class FixedPatternCorrelator(_Handle):
     """dsptl::FixedPatternCorrelator<int16_t, int32_t, N, S> (correlators.h:54-316)."""
