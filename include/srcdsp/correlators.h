@@ -148,6 +148,8 @@ public:
                              "getStatus");
         return s;
     }
+    /// the C ABI handle (DemodulatorOqpsk::setReference takes the bit samples from it)
+    srcdsp_corr_t handle() const { return h_; }
 
 private:
     srcdsp_corr_t h_;

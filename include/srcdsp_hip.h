@@ -310,6 +310,77 @@ SRCDSP_API int srcdsp_corr_get_status(srcdsp_corr_t h, uint32_t *energy3, uint32
                                       double *threshold_factor);
 
 /* ============================================================================
+ * DemodulatorOqpsk<int16_t>   (demodulators.h:53-130, demodulators.cpp:34-308)
+ * One sample per bit in, soft bits (int8) out.  The PLL makes one burst a
+ * sequential recurrence; the kernel runs one burst per lane, so the single
+ * step is provided for parity and state continuity (slower than a host core)
+ * and the bank, srcdsp_demod_step_batched, is the form to call.
+ * A handle is a host object (configuration and the 7 words of StateVar): each
+ * step uploads them with the reference samples its preamble reads and takes
+ * the new state back, so the set/get/reset/clone calls make no device call.
+ * A step returns with `stream` synchronised (the error is needed on the host),
+ * which also orders the steps of a handle across streams.
+ * ==========================================================================*/
+typedef struct srcdsp_demod *srcdsp_demod_t;
+/* ctor  demodulators.cpp:34-58 (the two lookup tables are process-wide) */
+SRCDSP_API int srcdsp_demod_create(srcdsp_demod_t *out);
+SRCDSP_API int srcdsp_demod_destroy(srcdsp_demod_t h);
+/* implicit copy (demodulators.h:53-130 is a value type): configuration and state */
+SRCDSP_API int srcdsp_demod_clone(srcdsp_demod_t h, srcdsp_demod_t *out);
+/* setSyncPattern  demodulators.h:60.  nbits = 0: no pattern; nbits = 1 is
+ * refused (reset() asserts, demodulators.cpp:302), as are bits other than 0 / 1
+ * (demodulators.h:94) */
+SRCDSP_API int srcdsp_demod_set_sync_pattern(srcdsp_demod_t h, const int8_t *bits, int nbits);
+/* setReference  demodulators.cpp:126-139 (n complex<int16_t>, host) */
+SRCDSP_API int srcdsp_demod_set_reference(srcdsp_demod_t h, const int16_t *ref_host, int n);
+/* setReference(corr.getRefBitSamples())  correlators.h:311-316,
+ * demodulators.h:67-68: the join with the correlator, without the caller's
+ * vector.  Takes the N bit samples the correlator's last detection left in its
+ * handle (its step is synchronous). */
+SRCDSP_API int srcdsp_demod_set_reference_corr(srcdsp_demod_t h, srcdsp_corr_t corr, void *stream);
+/* setInitialFrequency  demodulators.h:64.  A word outside +-4096 (the
+ * reference's phase goes negative and phaseShift asserts, :109): SRCDSP_ERR_ARG */
+SRCDSP_API int srcdsp_demod_set_initial_frequency(srcdsp_demod_t h, float f);
+/* setInitialPhase  demodulators.h:66 (stored only, as in the reference) */
+SRCDSP_API int srcdsp_demod_set_initial_phase(srcdsp_demod_t h, float p);
+/* setInputShift  demodulators.h:70; 0..15 */
+SRCDSP_API int srcdsp_demod_set_input_shift(srcdsp_demod_t h, int shift);
+/* reset  demodulators.cpp:293-308: StateVar cleared, the shift back to 0,
+ * bit1 / bit2 from the last two sync bits */
+SRCDSP_API int srcdsp_demod_reset(srcdsp_demod_t h);
+/* getMeasuredFrequency  demodulators.h:72 (0 before the first step) */
+SRCDSP_API int srcdsp_demod_get_measured_frequency(srcdsp_demod_t h, float *f);
+/* StateVar demodulators.h:76-88, then intialFreqEst, accumulatedFrequency, rightShift */
+SRCDSP_API int srcdsp_demod_get_state(srcdsp_demod_t h, unsigned *bit_cnt, int *mod2_cnt, int *phase, int *bit1,
+                                      int *bit2, int *i_prev, int *q_prev, int *freq_word, int *acc_freq, int *shift);
+/* sineLUT[8192] and phaseLUT[128 * 128] as the constructor builds them
+ * (demodulators.cpp:39-55); host arrays, no device call */
+SRCDSP_API int srcdsp_demod_get_tables(int16_t *sine8192_host, int16_t *phase16384_host);
+/* step  demodulators.cpp:150-284.  d_soft has room for cap int8; *n_soft =
+ * the size of the vector the reference returns (n, or n - P on the first call
+ * after reset with a pattern of P bits); cap < that -> SRCDSP_ERR_SIZE.  A first
+ * call with n <= P (:171 asserts) and a preamble longer than the reference
+ * vector (:196 reads past Iref) -> SRCDSP_ERR_SIZE; n > INT_MAX likewise.
+ * n = 0: SRCDSP_OK, nothing changes.  Synchronous like srcdsp_corr_step. */
+SRCDSP_API int srcdsp_demod_step(srcdsp_demod_t h, const void *d_in, size_t n, int8_t *d_soft, size_t cap,
+                                 size_t *n_soft, int32_t *error, void *stream);
+SRCDSP_API int srcdsp_demod_step_host(srcdsp_demod_t h, const void *in, size_t n, int8_t *soft, size_t cap,
+                                      size_t *n_soft, int32_t *error);
+/* Extension (no reference call).  C demodulators in one launch: channel c does
+ * exactly hs[c].step(in_c, error[c]), in_c = d_in + c*in_stride +
+ * (in_offset ? in_offset[c] : 0) samples, n samples each, soft bits to
+ * d_soft + c*soft_stride.  in_stride == 0: all channels read the same buffer
+ * (frequency hypotheses of one burst).  in_offset, n_soft, error: host arrays
+ * of `channels` entries (in_offset may be NULL).  Patterns, references, shifts,
+ * frequencies and states may differ per channel.  Every handle listed once;
+ * channels >= 1 (no upper limit); soft_stride >= the largest n_soft.  One
+ * upload, one launch and one host synchronisation per call whatever `channels`
+ * is.  A refused call changes no handle. */
+SRCDSP_API int srcdsp_demod_step_batched(const srcdsp_demod_t *hs, int channels, const void *d_in, size_t in_stride,
+                                         const size_t *in_offset, size_t n, int8_t *d_soft, size_t soft_stride,
+                                         size_t *n_soft, int32_t *error, void *stream);
+
+/* ============================================================================
  * FifoWithTimeTrack<T, N>   (buffers.h:58-459), the ring in HBM
  * One producer thread writes, one consumer thread reads (as the reference).
  * Element type T is opaque: elem_bytes per element.

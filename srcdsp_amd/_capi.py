@@ -80,6 +80,23 @@ SIGNATURES = {
     "srcdsp_corr_step_host_trace": (I, [VP, VP, SZ, IP, IP, U32P, U32P, C.POINTER(C.c_size_t)]),
     "srcdsp_corr_get_bit_samples": (I, [VP, I16P]),
     "srcdsp_corr_get_status": (I, [VP, U32P, U32P, U32P, IP, DP]),
+    "srcdsp_demod_create": (I, [HP]),
+    "srcdsp_demod_destroy": (I, [VP]),
+    "srcdsp_demod_clone": (I, [VP, HP]),
+    "srcdsp_demod_set_sync_pattern": (I, [VP, C.POINTER(C.c_int8), I]),
+    "srcdsp_demod_set_reference": (I, [VP, I16P, I]),
+    "srcdsp_demod_set_reference_corr": (I, [VP, VP, VP]),
+    "srcdsp_demod_set_initial_frequency": (I, [VP, F]),
+    "srcdsp_demod_set_initial_phase": (I, [VP, F]),
+    "srcdsp_demod_set_input_shift": (I, [VP, I]),
+    "srcdsp_demod_reset": (I, [VP]),
+    "srcdsp_demod_get_measured_frequency": (I, [VP, FP]),
+    "srcdsp_demod_get_state": (I, [VP, UP, IP, IP, IP, IP, IP, IP, IP, IP, IP]),
+    "srcdsp_demod_get_tables": (I, [I16P, I16P]),
+    "srcdsp_demod_step": (I, [VP, VP, SZ, VP, SZ, C.POINTER(C.c_size_t), I32P, VP]),
+    "srcdsp_demod_step_host": (I, [VP, VP, SZ, VP, SZ, C.POINTER(C.c_size_t), I32P]),
+    "srcdsp_demod_step_batched": (I, [HP, I, VP, SZ, C.POINTER(C.c_size_t), SZ, VP, SZ, C.POINTER(C.c_size_t), I32P,
+                                      VP]),
     "srcdsp_fifo_create": (I, [HP, SZ, SZ, D]),
     "srcdsp_fifo_destroy": (I, [VP]),
     "srcdsp_fifo_write": (I, [VP, VP, SZ, U, D]),

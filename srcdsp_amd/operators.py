@@ -591,6 +591,124 @@ def corr_batched_stats():
     return b.value, l.value
 
 
+# ============================================================== DemodulatorOqpsk
+class DemodulatorOqpsk(_Handle):
+    """dsptl::DemodulatorOqpsk<int16_t> (demodulators.h:53-130): one sample per
+    bit in, soft bits (int8) out.  One burst is a sequential recurrence and
+    runs on one GPU lane: a single step() is slower than a host core.  Step
+    many bursts at once with demod_step_batched()."""
+
+    _destroy = "srcdsp_demod_destroy"
+    _clone = "srcdsp_demod_clone"
+
+    def __init__(self, InType="int16_t"):
+        if _kind(InType) != "i16":
+            raise TypeError("DemodulatorOqpsk is provided for <int16_t>")
+        self._h = C.c_void_p()
+        A.call("srcdsp_demod_create", C.byref(self._h))
+
+    def setSyncPattern(self, bits):
+        b = np.ascontiguousarray(bits, np.int8).reshape(-1)
+        A.call("srcdsp_demod_set_sync_pattern", self._h, b.ctypes.data_as(C.POINTER(C.c_int8)), len(b))
+
+    def setReference(self, ref):
+        """ref: complex<int16_t> samples, int16 [n, 2] -- or a
+        FixedPatternCorrelator, whose bit samples (getRefBitSamples) are taken
+        from its handle."""
+        if isinstance(ref, FixedPatternCorrelator):
+            A.call("srcdsp_demod_set_reference_corr", self._h, ref._h, None)
+            return
+        r = np.ascontiguousarray(ref, np.int16).reshape(-1, 2)
+        A.call("srcdsp_demod_set_reference", self._h, r.ctypes.data_as(A.I16P), len(r))
+
+    def setInitialFrequency(self, f: float):
+        A.call("srcdsp_demod_set_initial_frequency", self._h, C.c_float(f))
+
+    def setInitialPhase(self, p: float):
+        A.call("srcdsp_demod_set_initial_phase", self._h, C.c_float(p))
+
+    def setInputShift(self, shift: int):
+        A.call("srcdsp_demod_set_input_shift", self._h, int(shift))
+
+    def reset(self):
+        A.call("srcdsp_demod_reset", self._h)
+
+    def getMeasuredFrequency(self) -> float:
+        f = C.c_float()
+        A.call("srcdsp_demod_get_measured_frequency", self._h, C.byref(f))
+        return f.value
+
+    set_sync_pattern, set_reference, set_initial_frequency = setSyncPattern, setReference, setInitialFrequency
+    set_initial_phase, set_input_shift, measured_frequency = setInitialPhase, setInputShift, getMeasuredFrequency
+
+    def state(self):
+        """(bitCnt, mod2Cnt, phase, bit1, bit2, Iprev, Qprev, intialFreqEst,
+        accumulatedFrequency, rightShift)."""
+        bc = C.c_uint()
+        v = [C.c_int() for _ in range(9)]
+        A.call("srcdsp_demod_get_state", self._h, C.byref(bc), *[C.byref(x) for x in v])
+        return (bc.value,) + tuple(x.value for x in v)
+
+    def step(self, inp):
+        """Returns (soft bits, error): an int8 device tensor for a device
+        input, an int8 numpy array for a host one."""
+        n = _nsamples(inp, "ci16")
+        ns, err = C.c_size_t(0), C.c_int32(0)
+        if _is_device(inp):
+            import torch
+            soft = torch.empty(max(n, 1), dtype=torch.int8, device=inp.device)
+            A.call("srcdsp_demod_step", self._h, _ptr(inp), n, _ptr(soft), n, C.byref(ns), C.byref(err), _stream(inp))
+        else:
+            x = _host(inp, "ci16")
+            soft = np.zeros(max(n, 1), np.int8)
+            A.call("srcdsp_demod_step_host", self._h, _ptr(x), n, _ptr(soft), n, C.byref(ns), C.byref(err))
+        return soft[:ns.value], err.value
+
+
+def demod_tables():
+    """(sineLUT int16[8192], phaseLUT int16[128 * 128]) as the library built them."""
+    s, p = np.zeros(8192, np.int16), np.zeros(128 * 128, np.int16)
+    A.call("srcdsp_demod_get_tables", s.ctypes.data_as(A.I16P), p.ctypes.data_as(A.I16P))
+    return s, p
+
+
+def demod_step_batched(demods, x, offsets=None, n=None):
+    """Step C demodulators in one launch: channel c is exactly
+    ``demods[c].step(x_c)``.  ``x`` is a device tensor of complex<int16_t>
+    samples: int16 [C, m, 2], one row per channel, or [m, 2], one buffer every
+    channel reads (frequency hypotheses of one burst).  ``offsets[c]`` (samples)
+    moves channel c's first sample within its row; every channel steps ``n``
+    samples (default: what the largest offset leaves of a row).  Returns
+    (soft int8 [C, n] device tensor, n_soft list, errors list): row c holds
+    n_soft[c] soft bits."""
+    import torch
+    ch = len(demods)
+    if ch < 1:
+        raise ValueError("demod_step_batched: at least one demodulator")
+    if not _is_device(x):
+        raise TypeError("demod_step_batched() takes a device-resident buffer")
+    if x.dim() not in (2, 3) or x.shape[-1] != 2 or x.element_size() != 2:
+        raise ValueError("demod_step_batched: x is int16 [m, 2] (shared) or [C, m, 2]")
+    shared = x.dim() == 2
+    if not shared and x.shape[0] != ch:
+        raise ValueError("demod_step_batched: one input row per demodulator")
+    m = x.shape[-2]
+    offs = [0] * ch if offsets is None else [int(o) for o in offsets]
+    if len(offs) != ch or min(offs) < 0 or max(offs) > m:
+        raise ValueError("demod_step_batched: one offset per channel, within the row")
+    if n is None:
+        n = m - max(offs)
+    if n < 0 or max(offs) + n > m:
+        raise ValueError("demod_step_batched: offset + n runs past the row")
+    hs = (C.c_void_p * ch)(*[d._h.value for d in demods])
+    off = (C.c_size_t * ch)(*offs)
+    ns, err = (C.c_size_t * ch)(), (C.c_int32 * ch)()
+    soft = torch.empty((ch, max(n, 1)), dtype=torch.int8, device=x.device)
+    A.call("srcdsp_demod_step_batched", hs, ch, _ptr(x), 0 if shared else m, off, n, _ptr(soft), max(n, 1), ns, err,
+           _stream(x))
+    return soft[:, :n], list(ns), list(err)
+
+
 def fill_synthetic(t, kind: str, seed: int = 0x5EED, channel: int = 0, offset: int = 0, lo: int = -2048,
                    hi: int = 2047):
     """Fill a device tensor with the counter-based synthetic samples."""
