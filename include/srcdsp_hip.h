@@ -381,7 +381,73 @@ SRCDSP_API int srcdsp_demod_step_batched(const srcdsp_demod_t *hs, int channels,
                                          size_t *n_soft, int32_t *error, void *stream);
 
 /* ============================================================================
- * FifoWithTimeTrack<T, N>   (buffers.h:58-459), the ring in HBM
+ * estimateFreq<int16_t, L>   (dsptl_miscellaneous.h:43-58)
+ * The frequency of n complex<int16_t> samples in rad/sample from the lag-L
+ * autocorrelation sum x[i] * conj(x[i+L]), i < n - L (for e^{+jwn} it returns
+ * -w, as the reference does).  Every term is an int, so the sums are taken
+ * exactly in 64-bit integers, in any order:
+ *   sums[0], sums[1]  the exact sums of termI, termQ.  termI at
+ *                     x[i] = x[i+L] = (-32768, -32768) is the two's complement
+ *                     wrap, -2^31 (undefined in the reference);
+ *   *freq             (float)(atan2((double)sums[1], (double)sums[0]) / L),
+ *                     the atan2 on the host;
+ *   *exact            1 iff (n - L) * T < 2^53, T the largest |termI| or
+ *                     |termQ| of the call (|-2^31| = 2^31; from the largest
+ *                     and the smallest term, which the kernel tracks): then no
+ *                     partial sum of the reference's double accumulation was
+ *                     rounded and *freq is the reference's float bit for bit.
+ *                     With 0 it comes from the exact sums and may differ from
+ *                     the reference's in the last bits.  1 when n <= L.
+ * A handle holds L and the scratch of its calls, no signal state.  The calls
+ * are synchronous like srcdsp_corr_step (the answer is needed on the host):
+ * one copy of 4 words per row back and one synchronisation per call.  sums
+ * and exact may be NULL.  n <= L (n = 0 included): SRCDSP_OK, zeros, +0.0f,
+ * no device call.  n > INT_MAX: SRCDSP_ERR_SIZE.  Only InType = int16_t: the
+ * float instantiation adds rounded products to a running double in order,
+ * which a parallel sum cannot reproduce.
+ * ==========================================================================*/
+typedef struct srcdsp_freqest *srcdsp_freqest_t;
+SRCDSP_API int srcdsp_freqest_create(srcdsp_freqest_t *out, int L); /* L >= 1; no device call */
+SRCDSP_API int srcdsp_freqest_destroy(srcdsp_freqest_t h);
+/* L, and the kernel's geometry: pairs per tile, samples per vector load, and
+ * the persistent workgroups of a launch on the current device (asks the
+ * device; the others make no device call).  Any pointer may be NULL. */
+SRCDSP_API int srcdsp_freqest_geometry(srcdsp_freqest_t h, int *L, int *tile, int *vec, int *workgroups);
+/* one row of n samples in device memory, reduced by the whole GPU */
+SRCDSP_API int srcdsp_freqest_run(srcdsp_freqest_t h, const void *d_in, size_t n, float *freq, int64_t sums[2],
+                                  int *exact, void *stream);
+/* host input, staged through pinned memory, the same kernel */
+SRCDSP_API int srcdsp_freqest_run_host(srcdsp_freqest_t h, const void *in, size_t n, float *freq, int64_t sums[2],
+                                       int *exact);
+/* Extension (no reference call).  `channels` rows in one launch: row c is
+ * d_in + c*in_stride + (in_offset ? in_offset[c] : 0) samples, n samples each;
+ * in_stride == 0: every row lies in one buffer.  freq, exact: `channels`
+ * entries; sums: 2 per channel.  No pair spans two rows and no load passes the
+ * end of a row. */
+SRCDSP_API int srcdsp_freqest_run_batched(srcdsp_freqest_t h, int channels, const void *d_in, size_t in_stride,
+                                          const size_t *in_offset, size_t n, float *freq, int64_t *sums, int *exact,
+                                          void *stream);
+/* Extension: the join of the correlator bank and the demodulator bank.  For
+ * every channel c taken (found == NULL, or found[c] != 0):
+ *   demods[c].setReference(cors[c].getRefBitSamples()), all N samples, as
+ *   srcdsp_demod_set_reference_corr; est = estimateFreq<int16_t, L> over bit
+ *   samples first .. N-1; setInitialFrequency(scale * est), the product in
+ *   float and the word rule of srcdsp_demod_set_initial_frequency; reset();
+ *   freq[c] = est (freq may be NULL).
+ * first = 0 is the literal composition estimateFreq(getRefBitSamples());
+ * first = 1 leaves out slot 0, which holds the detected sample and not a
+ * preamble sample (correlators.h:278-288).  scale = -1 turns the estimator's
+ * sign into the demodulator's.  Channels not taken are untouched and their
+ * freq[c] is not written.  All or nothing: a word outside +-4096, first
+ * outside 0..N-1, L < 1, a null handle of a taken channel, or a demodulator
+ * taken twice -> SRCDSP_ERR_ARG and no handle changes.  The bit samples are
+ * in the correlator's host-side handle, so the join makes no launch: its
+ * arithmetic is the kernel's per-pair function on the host. */
+SRCDSP_API int srcdsp_demod_acquire_batched(const srcdsp_demod_t *demods, const srcdsp_corr_t *cors, int channels,
+                                            const int *found, int L, int first, float scale, float *freq);
+
+/* ============================================================================
+ * FifoWithTimeTrack<T, N>  (buffers.h:58-459), the ring in HBM
  * One producer thread writes, one consumer thread reads (as the reference).
  * Element type T is opaque: elem_bytes per element.
  * ==========================================================================*/

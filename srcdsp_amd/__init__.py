@@ -1,14 +1,17 @@
 """srcdsp_amd -- MI355X (gfx950) implementation of SrcDsp's sample-buffer hot path.
 
 The operators (FilterDnsamplingFir, FilterFir, FilterUpsamplingFir, Mixer,
-FixedPatternCorrelator, DemodulatorOqpsk, FifoWithTimeTrack; files.read/saveBinarySamples) mirror the reference classes and run in the HIP
+FixedPatternCorrelator, DemodulatorOqpsk, FifoWithTimeTrack; estimateFreq (FreqEstimator); files.read/saveBinarySamples) mirror the reference classes and run in the HIP
 kernels of libsrcdsp_hip.so through its C ABI (include/srcdsp_hip.h).
 """
 from ._capi import SrcdspError, lib  # noqa: F401
 from . import files  # noqa: F401
 from .operators import (  # noqa: F401
     DemodulatorOqpsk,
+    demod_acquire_batched,
     demod_step_batched,
+    estimate_freq,
+    FreqEstimator,
     demod_tables,
     FifoWithTimeTrack,
     FilterDnsamplingFir,
@@ -32,4 +35,5 @@ __all__ = ["FifoWithTimeTrack", "files", "FilterDnsamplingFir", "FilterFir", "Fi
            "UpsamplerMixerChain", "upmix_step_batched", "upmix_stats",
            "FixedPatternCorrelator", "decim_step_batched", "mixdecim_step_batched", "mixdecim_batched_stats",
            "corr_step_batched", "corr_batched_stats", "DemodulatorOqpsk", "demod_step_batched", "demod_tables",
+           "FreqEstimator", "estimate_freq", "demod_acquire_batched",
            "fill_synthetic", "SrcdspError", "lib"]

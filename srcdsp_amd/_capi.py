@@ -97,6 +97,13 @@ SIGNATURES = {
     "srcdsp_demod_step_host": (I, [VP, VP, SZ, VP, SZ, C.POINTER(C.c_size_t), I32P]),
     "srcdsp_demod_step_batched": (I, [HP, I, VP, SZ, C.POINTER(C.c_size_t), SZ, VP, SZ, C.POINTER(C.c_size_t), I32P,
                                       VP]),
+    "srcdsp_freqest_create": (I, [HP, I]),
+    "srcdsp_freqest_destroy": (I, [VP]),
+    "srcdsp_freqest_geometry": (I, [VP, IP, IP, IP, IP]),
+    "srcdsp_freqest_run": (I, [VP, VP, SZ, FP, C.POINTER(C.c_int64), IP, VP]),
+    "srcdsp_freqest_run_host": (I, [VP, VP, SZ, FP, C.POINTER(C.c_int64), IP]),
+    "srcdsp_freqest_run_batched": (I, [VP, I, VP, SZ, C.POINTER(C.c_size_t), SZ, FP, C.POINTER(C.c_int64), IP, VP]),
+    "srcdsp_demod_acquire_batched": (I, [HP, HP, I, IP, I, I, F, FP]),
     "srcdsp_fifo_create": (I, [HP, SZ, SZ, D]),
     "srcdsp_fifo_destroy": (I, [VP]),
     "srcdsp_fifo_write": (I, [VP, VP, SZ, U, D]),

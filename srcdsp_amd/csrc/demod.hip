@@ -23,6 +23,7 @@
 #include "ops.h"
 #include "corr_state.h"
 #include "demod_kernels.h"
+#include "freqest_pair.h"
 
 namespace srcdsp {
 
@@ -500,6 +501,56 @@ SRCDSP_API int srcdsp_demod_step_host(srcdsp_demod_t h, const void *in, size_t n
         memcpy(soft, h_soft, ns);
     }
     *n_soft = ns;
+    return SRCDSP_OK;
+}
+
+// The join of the correlator bank and the demodulator bank: per taken channel
+// setReference(corr.getRefBitSamples()), estimateFreq<int16_t, L>
+// (dsptl_miscellaneous.h:43-58) over bit samples first .. N - 1,
+// setInitialFrequency(scale * est), reset().  The bit samples are in the
+// correlator's host-side handle, so nothing is launched: the estimate is
+// freqest_pair, the kernel's per-pair arithmetic, on the host.  Every check
+// comes before the first handle changes.
+SRCDSP_API int srcdsp_demod_acquire_batched(const srcdsp_demod_t *demods, const srcdsp_corr_t *cors, int channels,
+                                            const int *found, int L, int first, float scale, float *freq) {
+    SRCDSP_ARG_CHECK(demods != nullptr && cors != nullptr, "demod_acquire_batched: no handles");
+    SRCDSP_ARG_CHECK(channels >= 1, "demod_acquire_batched: channels is at least 1");
+    SRCDSP_ARG_CHECK(L >= 1, "demod_acquire_batched: L is at least 1");
+    std::vector<const void *> taken;
+    for (int c = 0; c < channels; ++c) {
+        if (found && !found[c]) continue;
+        SRCDSP_ARG_CHECK(demods[c] != nullptr && cors[c] != nullptr, "demod_acquire_batched: null handle");
+        SRCDSP_ARG_CHECK(first >= 0 && (unsigned)first < cors[c]->c.N,
+                         "demod_acquire_batched: first outside 0..N-1 of a correlator");
+        taken.push_back(demods[c]);
+    }
+    std::sort(taken.begin(), taken.end());
+    SRCDSP_ARG_CHECK(std::adjacent_find(taken.begin(), taken.end()) == taken.end(),
+                     "demod_acquire_batched: every demodulator may be listed once");
+    std::vector<float> est((size_t)channels, 0.0f);
+    std::vector<int> word((size_t)channels, 0);
+    for (int c = 0; c < channels; ++c) {
+        if (found && !found[c]) continue;
+        srcdsp_corr_state &k = cors[c]->c;
+        int rc = k.order.sync();
+        if (rc) return rc;
+        const FreqAcc a = freqest_row_host((const uint32_t *)k.bits.data() + first, k.N - (size_t)first, (size_t)L);
+        est[c] = static_cast<float>(std::atan2((double)a.sq, (double)a.si) / L);
+        const float f = scale * est[c];
+        const double w = std::round((double)(f * (float)4096) / kDemodPi);
+        SRCDSP_ARG_CHECK(w >= -4096.0 && w <= 4096.0, "demod_acquire_batched: frequency word outside +-4096");
+        word[c] = (int)w;
+    }
+    for (int c = 0; c < channels; ++c) {
+        if (found && !found[c]) continue;
+        DemodState &d = demods[c]->d;
+        const srcdsp_corr_state &k = cors[c]->c;
+        d.ref.resize(k.N);
+        memcpy(d.ref.data(), k.bits.data(), 4 * (size_t)k.N);
+        d.freq = word[c];
+        d.reset();
+        if (freq) freq[c] = est[c];
+    }
     return SRCDSP_OK;
 }
 

@@ -709,6 +709,105 @@ def demod_step_batched(demods, x, offsets=None, n=None):
     return soft[:, :n], list(ns), list(err)
 
 
+# ================================================================== estimateFreq
+class FreqEstimator(_Handle):
+    """estimateFreq<int16_t, L> (dsptl_miscellaneous.h:43-58): the frequency of
+    complex<int16_t> samples in rad/sample from their lag-L autocorrelation
+    (-w for e^{+jwn}, as the reference).  The sums are exact 64-bit integers;
+    ``exact`` tells that the float is the reference's bit for bit
+    (include/srcdsp_hip.h).  The handle holds L and scratch, no signal state."""
+
+    _destroy = "srcdsp_freqest_destroy"
+
+    def __init__(self, L: int = 1, InType="int16_t"):
+        if _kind(InType) != "i16":
+            raise TypeError("estimateFreq is provided for <int16_t, L>")
+        self.L = int(L)
+        self._h = C.c_void_p()
+        A.call("srcdsp_freqest_create", C.byref(self._h), self.L)
+
+    def geometry(self, device: bool = True):
+        """(tile, vec, workgroups): pairs per tile, samples per vector load and
+        (device=True) the persistent workgroups of a launch on this device."""
+        t, v, w = C.c_int(), C.c_int(), C.c_int()
+        A.call("srcdsp_freqest_geometry", self._h, None, C.byref(t), C.byref(v), C.byref(w) if device else None)
+        return t.value, v.value, w.value
+
+    def run(self, x):
+        """(freq, (sumI, sumQ), exact) of one buffer: a device tensor or a host
+        array of complex<int16_t> samples, int16 [n, 2]."""
+        n = _nsamples(x, "ci16")
+        f, s, e = C.c_float(), (C.c_int64 * 2)(), C.c_int()
+        if _is_device(x):
+            A.call("srcdsp_freqest_run", self._h, _ptr(x), n, C.byref(f), s, C.byref(e), _stream(x))
+        else:
+            h = _host(x, "ci16")
+            A.call("srcdsp_freqest_run_host", self._h, _ptr(h), n, C.byref(f), s, C.byref(e))
+        return np.float32(f.value), (s[0], s[1]), bool(e.value)
+
+    def run_batched(self, x, offsets=None, n=None, shared=False):
+        """C rows in one launch.  ``x`` is a device tensor of complex<int16_t>
+        samples: int16 [C, m, 2], one row per channel, or with ``shared`` [m, 2],
+        one buffer every row lies in (one row per offset).  ``offsets[c]``
+        (samples) moves row c's first sample; every row has ``n`` samples
+        (default: what the largest offset leaves).  Returns (freq float32 [C],
+        sums int64 [C, 2], exact bool [C]), row c as ``run`` of that row."""
+        if not _is_device(x):
+            raise TypeError("FreqEstimator.run_batched() takes a device-resident buffer")
+        if x.dim() != (2 if shared else 3) or x.shape[-1] != 2 or x.element_size() != 2:
+            raise ValueError("FreqEstimator.run_batched: x is int16 [C, m, 2], or [m, 2] with shared")
+        m = x.shape[-2]
+        if shared:
+            if offsets is None:
+                raise ValueError("FreqEstimator.run_batched: a shared buffer needs one offset per row")
+            ch = len(offsets)
+        else:
+            ch = x.shape[0]
+        if ch < 1:
+            raise ValueError("FreqEstimator.run_batched: at least one row")
+        offs = [0] * ch if offsets is None else [int(o) for o in offsets]
+        if len(offs) != ch or min(offs) < 0 or max(offs) > m:
+            raise ValueError("FreqEstimator.run_batched: one offset per row, within the row")
+        if n is None:
+            n = m - max(offs)
+        if n < 0 or max(offs) + n > m:
+            raise ValueError("FreqEstimator.run_batched: offset + n runs past the row")
+        f, s, e = np.zeros(ch, np.float32), np.zeros((ch, 2), np.int64), np.zeros(ch, np.intc)
+        off = None if offsets is None else (C.c_size_t * ch)(*offs)
+        A.call("srcdsp_freqest_run_batched", self._h, ch, _ptr(x), 0 if shared else m, off, n,
+               f.ctypes.data_as(A.FP), s.ctypes.data_as(C.POINTER(C.c_int64)), e.ctypes.data_as(A.IP), _stream(x))
+        return f, s, e.astype(bool)
+
+
+def estimate_freq(x, L: int = 1):
+    """estimateFreq<int16_t, L>(x) (dsptl_miscellaneous.h:43-58) as float32."""
+    return FreqEstimator(L).run(x)[0]
+
+
+def demod_acquire_batched(demods, cors, found=None, L=1, first=1, scale=-1.0):
+    """The join of corr_step_batched and demod_step_batched.  For every channel
+    c taken (``found`` None, or found[c] true): demods[c] takes cors[c]'s bit
+    samples as its reference, estimateFreq<int16_t, L> over bit samples
+    first .. N-1 times ``scale`` as its initial frequency, and is reset.
+    ``first=1`` leaves out slot 0 of the bit samples, which is the detected
+    sample and not a preamble sample; ``scale=-1`` turns the estimator's sign
+    (-w for e^{+jwn}) into the demodulator's.  All or nothing (SrcdspError and
+    no handle changed).  Returns the estimates, float32 [C] (nan where not
+    taken).  Host code: no launch."""
+    ch = len(demods)
+    if ch < 1 or len(cors) != ch:
+        raise ValueError("demod_acquire_batched: one correlator per demodulator, at least one")
+    if found is not None and len(found) != ch:
+        raise ValueError("demod_acquire_batched: one found flag per channel")
+    hd = (C.c_void_p * ch)(*[d._h.value for d in demods])
+    hc = (C.c_void_p * ch)(*[c._h.value for c in cors])
+    fl = None if found is None else (C.c_int * ch)(*[int(bool(v)) for v in found])
+    f = np.full(ch, np.nan, np.float32)
+    A.call("srcdsp_demod_acquire_batched", hd, hc, ch, fl, int(L), int(first), C.c_float(scale),
+           f.ctypes.data_as(A.FP))
+    return f
+
+
 def fill_synthetic(t, kind: str, seed: int = 0x5EED, channel: int = 0, offset: int = 0, lo: int = -2048,
                    hi: int = 2047):
     """Fill a device tensor with the counter-based synthetic samples."""
