@@ -98,7 +98,9 @@ SRCDSP_API int srcdsp_decim_step_host(srcdsp_decim_t h, const void *in, size_t n
                                       size_t n_out);
 /* C channels of one configuration in one launch (grid.y = channel).  Channel c
  * reads d_in + c*in_stride samples and writes d_out + c*out_stride samples;
- * each handle keeps its own history.  All handles must share variant, M, taps. */
+ * each handle keeps its own history.  All handles must share variant, M, taps;
+ * every handle is non-null and listed once (SRCDSP_ERR_ARG otherwise, before
+ * anything is enqueued: a refused call changes no handle). */
 SRCDSP_API int srcdsp_decim_step_batched(const srcdsp_decim_t *hs, int channels, const void *d_in,
                                          size_t in_stride, void *d_out, size_t out_stride,
                                          size_t n_in, void *stream);

@@ -154,7 +154,7 @@ PATCHES["corrmfma"] = [
     ("corr.hip", "    c.cur = 0;\n    *out = n;\n",
      "    c.cur = 0;\n    rc = corr_mfma_prepare(c);\n    if (rc) {\n        srcdsp_corr_destroy(n);\n"
      "        return rc;\n    }\n    *out = n;\n"),
-    ("corr.hip", "(void *)c.d_bank})", "(void *)c.d_bank, (void *)c.d_mfma_b, (void *)c.d_seams})"),
+    ("corr.hip", "(void *)c.d_best})", "(void *)c.d_best, (void *)c.d_mfma_b, (void *)c.d_seams})"),
 ]
 
 # variants whose patch sites the product sources have since moved past (the

@@ -15,6 +15,7 @@
 #include <type_traits>
 
 #include "../../include/srcdsp_hip.h"
+#include "bank_host.h"
 
 namespace srcdsp {
 
@@ -138,13 +139,13 @@ struct Ordering {
 // Pinned host staging + an owned stream for the *_step_host entry points.
 struct HostStage {
     hipStream_t stream = nullptr;
-    void *h_buf = nullptr;
-    size_t h_cap = 0;
-    void *d_buf = nullptr;
-    size_t d_cap = 0;
+    void *h_buf = nullptr, *d_buf = nullptr;  // as the last reserve() left them
     int init();
     int reserve(size_t host_bytes, size_t dev_bytes);
     void destroy();
+
+  private:
+    GrowBuf pinned{GrowBuf::kPinned}, device{GrowBuf::kDevice};
 };
 
 int sample_bytes(int kind);  // 0 cf32, 1 ci16, 2 ci32, 3 f32, 4 i16, 5 i32

@@ -269,17 +269,6 @@ __global__ __launch_bounds__(256) void corr_point(const uint32_t *__restrict__ i
 }
 
 // ---------------------------------------------------------------- host side
-static int corr_alloc_scratch(srcdsp_corr_state &c, size_t n) {
-    if (n <= c.scratch_cap) return SRCDSP_OK;
-    if (c.d_corr) (void)hipFree(c.d_corr);
-    if (c.d_en) (void)hipFree(c.d_en);
-    c.d_corr = c.d_en = nullptr;
-    SRCDSP_HIP_TRY(hipMalloc(&c.d_corr, 4 * n));
-    SRCDSP_HIP_TRY(hipMalloc(&c.d_en, 4 * n));
-    c.scratch_cap = n;
-    return SRCDSP_OK;
-}
-
 // detect = false: stream the samples with no detection test (corr_prime):
 // only the last three positions are evaluated (they feed the registers).
 // trace (CREATE_DEBUG_FILES, correlators.h:253-257): host arrays of n_
@@ -318,9 +307,11 @@ static int corr_run(srcdsp_corr_state &c, const uint32_t *d_in, size_t n_, int *
     // for corr_detect
     const bool fused = fast && detect && !trace;
     if (!fused) {
-        rc = corr_alloc_scratch(c, n_);
+        rc = c.corr_vals.reserve(4 * n_);
+        if (!rc) rc = c.en_vals.reserve(4 * n_);
         if (rc) return rc;
     }
+    uint32_t *const d_corr = c.corr_vals.dev<uint32_t>(), *const d_en = c.en_vals.dev<uint32_t>();
     // The reference stops at the first detection (break, correlators.h:291).
     // All segments are queued at once; each launch returns at its start when
     // an earlier segment's detect kernel has recorded a hit, so the scan stops
@@ -350,22 +341,22 @@ static int corr_run(srcdsp_corr_state &c, const uint32_t *d_in, size_t n_, int *
             const long blocks = (per_phase + TO - 1) / TO;
             const size_t smem = 4 * (size_t)corr_lds_words((int)c.NP);
             hipLaunchKernelGGL(corr_eval_dot2, dim3((unsigned)blocks, c.S), dim3(kCBlock), smem, s, d_in, n, sb, se,
-                               hist, c.d_ptaps, (int)c.N, (int)c.NP, (int)c.S, cs, c.d_corr, c.d_en,
+                               hist, c.d_ptaps, (int)c.N, (int)c.NP, (int)c.S, cs, d_corr, d_en,
                                (const unsigned *)c.d_best);
         } else {
             const size_t smem = 4 * (size_t)((kCorrBlock + NSm1 + 3) & ~3l) + 8 * (size_t)c.N;
             const long blocks = (se - sb + kCorrBlock - 1) / kCorrBlock;
             if (smem <= kCorrEvalMaxSmem)
                 hipLaunchKernelGGL(corr_eval, dim3((unsigned)blocks), dim3(kCorrBlock), smem, s, d_in, n, sb, se, hist,
-                                   c.d_coef, c.N, c.S, cs, c.d_corr, c.d_en, (const unsigned *)c.d_best);
+                                   c.d_coef, c.N, c.S, cs, d_corr, d_en, (const unsigned *)c.d_best);
             else
                 hipLaunchKernelGGL(corr_eval_g, dim3((unsigned)blocks), dim3(kCorrBlock), 0, s, d_in, n, sb, se, hist,
-                                   c.d_coef, c.N, c.S, cs, c.d_corr, c.d_en, (const unsigned *)c.d_best);
+                                   c.d_coef, c.N, c.S, cs, d_corr, d_en, (const unsigned *)c.d_best);
         }
         SRCDSP_HIP_TRY(hipGetLastError());
         if (!detect) continue;
         const int db = (int)std::max<long>(1, std::min<long>((se - sb + 255) / 256, 4096));
-        hipLaunchKernelGGL(corr_detect, dim3(db), dim3(256), 0, s, c.d_corr, c.d_en, sb, se, c.corr[0], c.corr[1],
+        hipLaunchKernelGGL(corr_detect, dim3(db), dim3(256), 0, s, d_corr, d_en, sb, se, c.corr[0], c.corr[1],
                            c.energy[0], c.d_best);
         SRCDSP_HIP_TRY(hipGetLastError());
     }
@@ -377,8 +368,8 @@ static int corr_run(srcdsp_corr_state &c, const uint32_t *d_in, size_t n_, int *
     const bool hit = best != none;
     const long last = hit ? (long)best : n - 1;  // last processed sample
     if (trace) {  // every processed sample's registers (the segmented kernels computed them all up to `last`)
-        SRCDSP_HIP_TRY(hipMemcpyAsync(trace->corr, c.d_corr, 4 * (size_t)(last + 1), hipMemcpyDeviceToHost, s));
-        SRCDSP_HIP_TRY(hipMemcpyAsync(trace->energy, c.d_en, 4 * (size_t)(last + 1), hipMemcpyDeviceToHost, s));
+        SRCDSP_HIP_TRY(hipMemcpyAsync(trace->corr, d_corr, 4 * (size_t)(last + 1), hipMemcpyDeviceToHost, s));
+        SRCDSP_HIP_TRY(hipMemcpyAsync(trace->energy, d_en, 4 * (size_t)(last + 1), hipMemcpyDeviceToHost, s));
         SRCDSP_HIP_TRY(hipStreamSynchronize(s));
         *trace->count = (size_t)(last + 1);
     }
@@ -392,8 +383,8 @@ static int corr_run(srcdsp_corr_state &c, const uint32_t *d_in, size_t n_, int *
             ew[idx - lo] = words[5 + (last - idx)];
         }
     } else {
-        SRCDSP_HIP_TRY(hipMemcpyAsync(cw, c.d_corr + lo, 4 * cnt, hipMemcpyDeviceToHost, s));
-        SRCDSP_HIP_TRY(hipMemcpyAsync(ew, c.d_en + lo, 4 * cnt, hipMemcpyDeviceToHost, s));
+        SRCDSP_HIP_TRY(hipMemcpyAsync(cw, d_corr + lo, 4 * cnt, hipMemcpyDeviceToHost, s));
+        SRCDSP_HIP_TRY(hipMemcpyAsync(ew, d_en + lo, 4 * cnt, hipMemcpyDeviceToHost, s));
         SRCDSP_HIP_TRY(hipStreamSynchronize(s));
     }
     uint32_t nc[3], ne[3];
@@ -526,10 +517,11 @@ SRCDSP_API int srcdsp_corr_destroy(srcdsp_corr_t h) {
     if (!h) return SRCDSP_OK;
     srcdsp_corr_state &c = h->c;
     (void)c.order.sync();
-    for (void *p : {(void *)c.d_coef, (void *)c.d_ptaps, (void *)c.d_hist[0], (void *)c.d_hist[1], (void *)c.d_corr, (void *)c.d_en,
-                    (void *)c.d_best, (void *)c.d_bank})
+    for (void *p : {(void *)c.d_coef, (void *)c.d_ptaps, (void *)c.d_hist[0], (void *)c.d_hist[1], (void *)c.d_best})
         if (p) (void)hipFree(p);
-    if (c.h_bank) (void)hipHostFree(c.h_bank);
+    c.corr_vals.destroy();
+    c.en_vals.destroy();
+    c.bank.destroy();
     c.order.destroy();
     c.stage.destroy();
     delete h;

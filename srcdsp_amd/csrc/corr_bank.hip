@@ -15,8 +15,6 @@
 // loop of srcdsp_corr_step over the channels.  Either way every handle is left
 // bit for bit as srcdsp_corr_step leaves it.
 #include <algorithm>
-#include <atomic>
-#include <vector>
 
 #include "ops.h"
 #include "corr_state.h"
@@ -78,31 +76,18 @@ __global__ __launch_bounds__(256) void corr_bank_finish(const CorrBankArgs A) {
 }
 
 namespace {
-std::atomic<unsigned long> g_bank_calls{0}, g_loop_calls{0};
-
-// hs[0]'s scratch: device best[C] | res[C][kRow] | bits[C][N], pinned host res | bits
-int bank_reserve(srcdsp_corr_state &lead, size_t channels) {
-    const size_t words = channels * (1 + kRow + (size_t)lead.N);
-    if (words <= lead.bank_cap) return SRCDSP_OK;
-    if (lead.d_bank) (void)hipFree(lead.d_bank);
-    if (lead.h_bank) (void)hipHostFree(lead.h_bank);
-    lead.d_bank = lead.h_bank = nullptr;
-    lead.bank_cap = 0;
-    SRCDSP_HIP_TRY(hipMalloc(&lead.d_bank, 4 * words));
-    SRCDSP_HIP_TRY(hipHostMalloc(&lead.h_bank, 4 * words));
-    lead.bank_cap = words;
-    return SRCDSP_OK;
-}
+PathCounter g_bank_calls, g_loop_calls;
 
 int bank_run(const srcdsp_corr_t *hs, int channels, const uint32_t *d_in, size_t in_stride, long n, int *found,
              int *corr_index, hipStream_t s) {
     srcdsp_corr_state &lead = hs[0]->c;
     const size_t C = (size_t)channels, N = lead.N;
-    int rc = bank_reserve(lead, C);
+    // hs[0]'s scratch: device best[C] | res[C][kRow] | bits[C][N], pinned host res | bits
+    int rc = lead.bank.reserve(4 * C * (1 + kRow + N));
     if (rc) return rc;
-    unsigned *d_best = lead.d_bank;
-    uint32_t *d_res = lead.d_bank + C, *d_bits = d_res + kRow * C;
-    uint32_t *h_res = lead.h_bank, *h_bits = h_res + kRow * C;
+    unsigned *d_best = lead.bank.dev<unsigned>();
+    uint32_t *d_res = d_best + C, *d_bits = d_res + kRow * C;
+    uint32_t *h_res = lead.bank.host<uint32_t>(), *h_bits = h_res + kRow * C;
     for (int c = 0; c < channels; ++c) {
         rc = hs[c]->c.order.before(s);
         if (rc) return rc;
@@ -124,8 +109,7 @@ int bank_run(const srcdsp_corr_t *hs, int channels, const uint32_t *d_in, size_t
         A.bits = d_bits + N * c0;
         for (int k = 0; k < nc; ++k) {
             srcdsp_corr_state &c = hs[c0 + k]->c;
-            A.hist[k] = c.d_hist[c.cur];
-            A.hist_out[k] = c.d_hist[c.cur ^ 1];
+            hist_pair(c, A.hist[k], A.hist_out[k]);
             A.ptaps[k] = c.d_ptaps;
             A.coef[k] = c.d_coef;
             A.cs[k] = (unsigned)c.coeff_scaling;
@@ -195,18 +179,13 @@ SRCDSP_API int srcdsp_corr_step_batched(const srcdsp_corr_t *hs, int channels, c
                                         size_t n, int *found, int *corr_index, void *stream) {
     SRCDSP_ARG_CHECK(hs != nullptr && found != nullptr && corr_index != nullptr && channels >= 1,
                      "corr_step_batched: no handles or result arrays");
-    for (int c = 0; c < channels; ++c) SRCDSP_ARG_CHECK(hs[c] != nullptr, "corr_step_batched: null handle");
+    int rc = check_handles(hs, channels, "corr_step_batched");
+    if (rc) return rc;
     const srcdsp_corr_state &c0 = hs[0]->c;
     bool bank = corr_fused_shape(c0);
     for (int c = 1; c < channels; ++c) {
         SRCDSP_ARG_CHECK(hs[c]->c.N == c0.N && hs[c]->c.S == c0.S, "corr_step_batched: correlators must share N and S");
         bank = bank && corr_fused_shape(hs[c]->c);
-    }
-    {
-        std::vector<const void *> hv(hs, hs + channels);
-        std::sort(hv.begin(), hv.end());
-        SRCDSP_ARG_CHECK(std::adjacent_find(hv.begin(), hv.end()) == hv.end(),
-                         "corr_step_batched: every handle may be listed once");
     }
     for (int c = 0; c < channels; ++c) found[c] = 0;
     if (n == 0) return SRCDSP_OK;
@@ -216,21 +195,18 @@ SRCDSP_API int srcdsp_corr_step_batched(const srcdsp_corr_t *hs, int channels, c
     }
     SRCDSP_ARG_CHECK(d_in != nullptr, "corr_step_batched: null input");
     if (!bank) {
-        g_loop_calls.fetch_add(1, std::memory_order_relaxed);
-        for (int c = 0; c < channels; ++c) {
-            int rc = srcdsp_corr_step(hs[c], (const uint32_t *)d_in + (size_t)c * in_stride, n, found + c,
-                                      corr_index + c, stream);
-            if (rc) return rc;
-        }
-        return SRCDSP_OK;
+        g_loop_calls.hit();
+        for (int c = 0; c < channels && !rc; ++c)
+            rc = srcdsp_corr_step(hs[c], chan_row(d_in, c, in_stride), n, found + c, corr_index + c, stream);
+        return rc;
     }
-    g_bank_calls.fetch_add(1, std::memory_order_relaxed);
+    g_bank_calls.hit();
     return bank_run(hs, channels, (const uint32_t *)d_in, in_stride, (long)n, found, corr_index, (hipStream_t)stream);
 }
 
 SRCDSP_API int srcdsp_corr_batched_stats(unsigned long *bank_calls, unsigned long *loop_calls) {
-    if (bank_calls) *bank_calls = g_bank_calls.load(std::memory_order_relaxed);
-    if (loop_calls) *loop_calls = g_loop_calls.load(std::memory_order_relaxed);
+    g_bank_calls.read(bank_calls);
+    g_loop_calls.read(loop_calls);
     return SRCDSP_OK;
 }
 

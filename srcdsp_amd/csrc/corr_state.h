@@ -20,14 +20,12 @@ struct srcdsp_corr_state {
                                  // reference's energy assert holds)
     uint32_t *d_hist[2] = {nullptr, nullptr};  // last NS-1 effective samples (packed ci16)
     int cur = 0;
-    uint32_t *d_corr = nullptr, *d_en = nullptr;  // per-sample scratch
-    size_t scratch_cap = 0;
+    GrowBuf corr_vals{GrowBuf::kDevice}, en_vals{GrowBuf::kDevice};  // per-sample scratch of the segmented kernels
     unsigned *d_best = nullptr;
     // scratch of the batched calls this handle led (hs[0] of
     // srcdsp_corr_step_batched): per channel a best slot, a result row and a
-    // bitSamples row on the device, and their pinned host mirror; grow-only
-    uint32_t *d_bank = nullptr, *h_bank = nullptr;
-    size_t bank_cap = 0;  // words
+    // bitSamples row on the device, and their pinned host mirror
+    GrowBuf bank;
     // CorrState (correlators.h:59-81)
     uint32_t energy[3] = {0, 0, 0}, corr[3] = {0, 0, 0};
     uint32_t coeffs_energy = 0;

@@ -14,8 +14,6 @@
 // Either way the outputs and every handle's state (mixer phase, decimator
 // history) are those of that loop, bit for bit.
 #include <algorithm>
-#include <atomic>
-#include <vector>
 
 #include "ops.h"
 
@@ -23,7 +21,7 @@
 
 namespace srcdsp {
 namespace {
-std::atomic<unsigned long> g_bank_calls{0}, g_loop_calls{0};
+PathCounter g_bank_calls, g_loop_calls;
 
 // persistent grid: the resident capacity (256 CUs x 4 workgroups) twice over
 constexpr long kBankGridCap = 2048;
@@ -72,25 +70,19 @@ int bank_launch(const srcdsp_mixer_t *mixers, const srcdsp_decim_t *decims, int 
     const int ngroups = (nc + group - 1) / group;
     for (int c = 0; c < nc; ++c) {
         MixerState &m = mixers[c]->m;
-        FirCore &fc = decims[c]->core;
         int rc = m.order.before(s);
-        if (!rc) rc = fc.order.before(s);
+        if (!rc) rc = chan_begin(decims[c]->core, s, L.hist_in[c], L.hist_out[c]);
         if (rc) return rc;
-        L.mix[c] = (uint32_t)(uint16_t)m.phi | ((uint32_t)(uint16_t)m.freq << 16);
-        L.hist_in[c] = fc.d_hist[fc.cur];
-        L.hist_out[c] = fc.d_hist[fc.cur ^ 1];
+        L.mix[c] = m.word();
     }
     dim3 grid((unsigned)std::min<long>(L.ntiles, std::max<long>(1, kBankGridCap / ngroups)), (unsigned)ngroups);
     hipLaunchKernelGGL(ddc_bank_ci16, grid, dim3(kBankBlock), 0, s, L);
     SRCDSP_HIP_TRY(hipGetLastError());
     for (int c = 0; c < nc; ++c) {
         MixerState &m = mixers[c]->m;
-        FirCore &fc = decims[c]->core;
-        fc.cur ^= 1;
-        // mixer phase after the call: phi += n_in * freq (mod N), mixers.h:177
-        m.phi = (int16_t)(((unsigned long)(unsigned)m.phi + (unsigned long)(n_in % m.N) * (unsigned)m.freq) % m.N);
+        m.advance(n_in);
         int rc = m.order.after(s);
-        if (!rc) rc = fc.order.after(s);
+        if (!rc) rc = chan_commit(decims[c]->core, s);
         if (rc) return rc;
     }
     return SRCDSP_OK;
@@ -106,8 +98,9 @@ SRCDSP_API int srcdsp_mixdecim_step_batched(const srcdsp_mixer_t *mixers, const 
                                             const void *d_in, size_t in_stride, void *d_out, size_t out_stride,
                                             size_t n_in, void *stream) {
     SRCDSP_ARG_CHECK(mixers != nullptr && decims != nullptr && channels >= 1, "mixdecim_step_batched: no handles");
-    for (int c = 0; c < channels; ++c)
-        SRCDSP_ARG_CHECK(mixers[c] != nullptr && decims[c] != nullptr, "mixdecim_step_batched: null handle");
+    int rc = check_handles(mixers, channels, "mixdecim_step_batched");
+    if (!rc) rc = check_handles(decims, channels, "mixdecim_step_batched");
+    if (rc) return rc;
     const FirCore &f0 = decims[0]->core;
     const MixerState &m0 = mixers[0]->m;
     if (f0.kv != KV_CI16_I32 && f0.kv != KV_CI16_I16) {
@@ -121,40 +114,27 @@ SRCDSP_API int srcdsp_mixdecim_step_batched(const srcdsp_mixer_t *mixers, const 
                          "mixdecim_step_batched: decimators must share variant, M, taps, flags and shift");
         SRCDSP_ARG_CHECK(mixers[c]->m.N == m0.N, "mixdecim_step_batched: mixers must share N");
     }
-    {
-        std::vector<const void *> hm(mixers, mixers + channels), hd(decims, decims + channels);
-        std::sort(hm.begin(), hm.end());
-        std::sort(hd.begin(), hd.end());
-        SRCDSP_ARG_CHECK(std::adjacent_find(hm.begin(), hm.end()) == hm.end() &&
-                             std::adjacent_find(hd.begin(), hd.end()) == hd.end(),
-                         "mixdecim_step_batched: every handle may be listed once");
-    }
     SRCDSP_ARG_CHECK(n_in % f0.M == 0, "mixdecim_step_batched: n_in must be a multiple of M");
     if (n_in == 0) return SRCDSP_OK;
     SRCDSP_ARG_CHECK(d_in && d_out, "mixdecim_step_batched: null buffer");
     hipStream_t s = (hipStream_t)stream;
     if (!bank_takes(f0, m0, d_in, in_stride, n_in)) {
-        g_loop_calls.fetch_add(1, std::memory_order_relaxed);
-        for (int c = 0; c < channels; ++c) {
-            int rc = srcdsp_mixdecim_step(mixers[c], decims[c], (const char *)d_in + (size_t)c * in_stride * 4, n_in,
-                                          (char *)d_out + (size_t)c * out_stride * 4, n_in / f0.M, stream);
-            if (rc) return rc;
-        }
-        return SRCDSP_OK;
+        g_loop_calls.hit();
+        for (int c = 0; c < channels && !rc; ++c)
+            rc = srcdsp_mixdecim_step(mixers[c], decims[c], chan_row(d_in, c, in_stride), n_in,
+                                      chan_row(d_out, c, out_stride), n_in / f0.M, stream);
+        return rc;
     }
-    g_bank_calls.fetch_add(1, std::memory_order_relaxed);
-    for (int c0 = 0; c0 < channels; c0 += kMaxBatch) {
-        const int nc = std::min(kMaxBatch, channels - c0);
-        int rc = bank_launch(mixers + c0, decims + c0, nc, (const char *)d_in + (size_t)c0 * in_stride * 4, in_stride,
-                             (char *)d_out + (size_t)c0 * out_stride * 4, out_stride, n_in, s);
-        if (rc) return rc;
-    }
-    return SRCDSP_OK;
+    g_bank_calls.hit();
+    for (int c0 = 0; c0 < channels && !rc; c0 += kMaxBatch)
+        rc = bank_launch(mixers + c0, decims + c0, std::min(kMaxBatch, channels - c0), chan_row(d_in, c0, in_stride),
+                         in_stride, chan_row(d_out, c0, out_stride), out_stride, n_in, s);
+    return rc;
 }
 
 SRCDSP_API int srcdsp_mixdecim_batched_stats(unsigned long *bank_calls, unsigned long *loop_calls) {
-    if (bank_calls) *bank_calls = g_bank_calls.load(std::memory_order_relaxed);
-    if (loop_calls) *loop_calls = g_loop_calls.load(std::memory_order_relaxed);
+    g_bank_calls.read(bank_calls);
+    g_loop_calls.read(loop_calls);
     return SRCDSP_OK;
 }
 

@@ -613,6 +613,8 @@ SRCDSP_API int srcdsp_decim_step_batched(const srcdsp_decim_t *hs, int channels,
                                          size_t in_stride, void *d_out, size_t out_stride, size_t n_in,
                                          void *stream) {
     SRCDSP_ARG_CHECK(hs != nullptr && channels >= 1, "decim_step_batched: no handles");
+    int rc = check_handles(hs, channels, "decim_step_batched");
+    if (rc) return rc;
     FirCore &f0 = hs[0]->core;
     SRCDSP_ARG_CHECK(n_in % f0.M == 0, "decim_step_batched: n_in must be a multiple of M");
     for (int c = 1; c < channels; ++c) {
@@ -627,8 +629,8 @@ SRCDSP_API int srcdsp_decim_step_batched(const srcdsp_decim_t *hs, int channels,
     for (int c0 = 0; c0 < channels; c0 += kMaxBatch) {
         int nc = std::min(kMaxBatch, channels - c0);
         DecimLaunch L{};
-        L.in = (const char *)d_in + (size_t)c0 * in_stride * ib;
-        L.out = (char *)d_out + (size_t)c0 * out_stride * ob;
+        L.in = chan_row(d_in, c0, in_stride, ib);
+        L.out = chan_row(d_out, c0, out_stride, ob);
         L.coef = f0.d_coef;  // all channels share the taps (checked above)
         L.n_in = (long)n_in;
         L.n_out = (long)(n_in / f0.M);
@@ -636,21 +638,10 @@ SRCDSP_API int srcdsp_decim_step_batched(const srcdsp_decim_t *hs, int channels,
         L.out_stride = (long)out_stride;
         L.ntaps = f0.ntaps;
         L.shift = f0.shift();
-        for (int c = 0; c < nc; ++c) {
-            FirCore &fc = hs[c0 + c]->core;
-            int rc = fc.order.before(s);
-            if (rc) return rc;
-            L.hist_in[c] = fc.d_hist[fc.cur];
-            L.hist_out[c] = fc.d_hist[fc.cur ^ 1];
-        }
-        int rc = decim_launch(f0, L, nc, s, false);
+        for (int c = 0; c < nc && !rc; ++c) rc = chan_begin(hs[c0 + c]->core, s, L.hist_in[c], L.hist_out[c]);
+        if (!rc) rc = decim_launch(f0, L, nc, s, false);
+        for (int c = 0; c < nc && !rc; ++c) rc = chan_commit(hs[c0 + c]->core, s);
         if (rc) return rc;
-        for (int c = 0; c < nc; ++c) {
-            FirCore &fc = hs[c0 + c]->core;
-            fc.cur ^= 1;
-            rc = fc.order.after(s);
-            if (rc) return rc;
-        }
     }
     return SRCDSP_OK;
 }
@@ -729,21 +720,18 @@ SRCDSP_API int srcdsp_fir_step_host(srcdsp_fir_t h, const void *in, size_t n_in,
 static int mixdecim_unfused(srcdsp_mixer_t mixer, FirCore &f, const void *d_in, size_t n_in, void *d_out,
                             size_t n_out, hipStream_t s) {
     MixerState &m = mixer->m;
-    if (m.scratch_cap < n_in * 4) {  // grow: only after every earlier use is done
+    if (m.scratch.cap < n_in * 4) {  // grow: only after every earlier use is done
         int rc = f.order.sync();
         if (!rc) rc = m.order.sync();
         if (rc) return rc;
         SRCDSP_HIP_TRY(hipStreamSynchronize(s));
-        if (m.d_scratch) (void)hipFree(m.d_scratch);
-        m.d_scratch = nullptr;
-        m.scratch_cap = 0;
-        SRCDSP_HIP_TRY(hipMalloc(&m.d_scratch, n_in * 4));
-        m.scratch_cap = n_in * 4;
+        rc = m.scratch.reserve(n_in * 4);
+        if (rc) return rc;
     }
     int rc = f.order.before(s);
     if (rc) return rc;
-    rc = srcdsp_mixer_step(mixer, d_in, n_in, m.d_scratch, s);  // mixers.h:169-188
-    if (rc == SRCDSP_OK) rc = core_step(f, m.d_scratch, n_in, d_out, n_out, s, nullptr);
+    rc = srcdsp_mixer_step(mixer, d_in, n_in, m.scratch.d, s);  // mixers.h:169-188
+    if (rc == SRCDSP_OK) rc = core_step(f, m.scratch.d, n_in, d_out, n_out, s, nullptr);
     if (rc == SRCDSP_OK) rc = m.order.after(s);  // scratch released after its reader
     return rc;
 }
@@ -776,8 +764,7 @@ SRCDSP_API int srcdsp_mixdecim_step(srcdsp_mixer_t mixer, srcdsp_decim_t decim, 
         return mixdecim_unfused(mixer, f, d_in, n_in, d_out, n_out, s);
     }
     if (rc) return rc;
-    // mixer phase after the call: phi += n_in * freq (mod N), mixers.h:177
-    m.phi = (int16_t)(((unsigned long)(unsigned)m.phi + (unsigned long)(n_in % m.N) * (unsigned)m.freq) % m.N);
+    m.advance(n_in);
     return m.order.after(s);
 }
 

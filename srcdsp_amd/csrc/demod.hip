@@ -119,11 +119,8 @@ struct DemodState {
     int acc_freq = 0;              // accumulatedFrequency
     int32_t st[7] = {0, 0, 0, 0, 0, 0, 0};  // StateVar, DS_BITCNT .. DS_QPREV
     // scratch of the calls this handle led: the table on the device and its
-    // pinned host image, the result rows likewise; grow-only
-    void *d_tab = nullptr, *h_tab = nullptr;
-    size_t tab_cap = 0;
-    int32_t *d_res = nullptr, *h_res = nullptr;
-    size_t res_cap = 0;  // rows
+    // pinned host image, the result rows likewise
+    GrowBuf tab, res;
     HostStage stage;     // srcdsp_demod_step_host
 
     void reset() {  // demodulators.cpp:293-308
@@ -179,26 +176,15 @@ int demod_device_tables(const uint32_t **out) {
     return SRCDSP_OK;
 }
 
-int demod_reserve(DemodState &lead, size_t tab_bytes, size_t rows) {
-    if (tab_bytes > lead.tab_cap) {
-        if (lead.d_tab) (void)hipFree(lead.d_tab);
-        if (lead.h_tab) (void)hipHostFree(lead.h_tab);
-        lead.d_tab = lead.h_tab = nullptr;
-        lead.tab_cap = 0;
-        SRCDSP_HIP_TRY(hipMalloc(&lead.d_tab, tab_bytes));
-        SRCDSP_HIP_TRY(hipHostMalloc(&lead.h_tab, tab_bytes));
-        lead.tab_cap = tab_bytes;
-    }
-    if (rows > lead.res_cap) {
-        if (lead.d_res) (void)hipFree(lead.d_res);
-        if (lead.h_res) (void)hipHostFree(lead.h_res);
-        lead.d_res = lead.h_res = nullptr;
-        lead.res_cap = 0;
-        SRCDSP_HIP_TRY(hipMalloc(&lead.d_res, 4 * DS_WORDS * rows));
-        SRCDSP_HIP_TRY(hipHostMalloc(&lead.h_res, 4 * DS_WORDS * rows));
-        lead.res_cap = rows;
-    }
-    return SRCDSP_OK;
+// float rad/sample -> the table's frequency word (setInitialFrequency,
+// demodulators.h:64): the product in float, the division and round() in
+// double.  False for a word outside +-4096, which lets the reference's phase go
+// negative (phaseShift asserts, :109).
+bool demod_freq_word(float f, int *word) {
+    const double w = std::round((double)(f * (float)4096) / kDemodPi);
+    if (!(w >= -4096.0 && w <= 4096.0)) return false;
+    *word = (int)w;
+    return true;
 }
 
 // soft bits of a call of n samples (:167-175), and the reference samples its
@@ -247,12 +233,15 @@ int demod_run(const srcdsp_demod_t *hs, int channels, const uint32_t *d_in, size
     size_t ref_words = 0;
     for (size_t c = 0; c < C; ++c) ref_words += demod_ref_reads(hs[c]->d, n);
     const size_t tab_bytes = C * sizeof(DemodChan) + 4 * ref_words;
-    int rc = demod_reserve(lead, tab_bytes, C);
+    int rc = lead.tab.reserve(tab_bytes);
+    if (!rc) rc = lead.res.reserve(4 * DS_WORDS * C);
     if (rc) return rc;
+    const DemodChan *d_tab = lead.tab.dev<DemodChan>();
+    int32_t *d_res = lead.res.dev<int32_t>(), *h_res = lead.res.host<int32_t>();
     const uint32_t *d_tables = nullptr;
     rc = demod_device_tables(&d_tables);
     if (rc) return rc;
-    DemodChan *tab = (DemodChan *)lead.h_tab;
+    DemodChan *tab = lead.tab.host<DemodChan>();
     uint32_t *refs = (uint32_t *)(tab + C);
     size_t ref_at = 0;
     for (size_t c = 0; c < C; ++c) {
@@ -270,17 +259,16 @@ int demod_run(const srcdsp_demod_t *hs, int channels, const uint32_t *d_in, size
         if (t.ref_len) memcpy(refs + ref_at, d.ref.data(), 4 * (size_t)t.ref_len);
         ref_at += (size_t)t.ref_len;
     }
-    SRCDSP_HIP_TRY(hipMemcpyAsync(lead.d_tab, lead.h_tab, tab_bytes, hipMemcpyHostToDevice, s));
+    SRCDSP_HIP_TRY(hipMemcpyAsync(lead.tab.d, tab, tab_bytes, hipMemcpyHostToDevice, s));
     const unsigned blocks = (unsigned)((C + kDemodLanes - 1) / kDemodLanes);
-    hipLaunchKernelGGL(demod_bank, dim3(blocks), dim3(kDemodLanes), 0, s, (const DemodChan *)lead.d_tab, channels,
-                       (const uint32_t *)((const DemodChan *)lead.d_tab + C), d_in, (long)n, d_soft, d_tables,
-                       lead.d_res);
+    hipLaunchKernelGGL(demod_bank, dim3(blocks), dim3(kDemodLanes), 0, s, d_tab, channels,
+                       (const uint32_t *)(d_tab + C), d_in, (long)n, d_soft, d_tables, d_res);
     SRCDSP_HIP_TRY(hipGetLastError());
-    SRCDSP_HIP_TRY(hipMemcpyAsync(lead.h_res, lead.d_res, 4 * DS_WORDS * C, hipMemcpyDeviceToHost, s));
+    SRCDSP_HIP_TRY(hipMemcpyAsync(h_res, d_res, 4 * DS_WORDS * C, hipMemcpyDeviceToHost, s));
     SRCDSP_HIP_TRY(hipStreamSynchronize(s));
     for (size_t c = 0; c < C; ++c) {
         DemodState &d = hs[c]->d;
-        const int32_t *row = lead.h_res + DS_WORDS * c;
+        const int32_t *row = h_res + DS_WORDS * c;
         for (int k = 0; k < 7; ++k) d.st[k] = row[k];
         d.acc_freq = row[DS_ACCFREQ];
         error[c] = row[DS_ERROR];
@@ -302,10 +290,8 @@ SRCDSP_API int srcdsp_demod_create(srcdsp_demod_t *out) {
 SRCDSP_API int srcdsp_demod_destroy(srcdsp_demod_t h) {
     if (!h) return SRCDSP_OK;
     DemodState &d = h->d;
-    if (d.d_tab) (void)hipFree(d.d_tab);
-    if (d.h_tab) (void)hipHostFree(d.h_tab);
-    if (d.d_res) (void)hipFree(d.d_res);
-    if (d.h_res) (void)hipHostFree(d.h_res);
+    d.tab.destroy();
+    d.res.destroy();
     if (d.stage.stream) d.stage.destroy();
     delete h;
     return SRCDSP_OK;
@@ -358,14 +344,12 @@ SRCDSP_API int srcdsp_demod_set_reference_corr(srcdsp_demod_t h, srcdsp_corr_t c
     return SRCDSP_OK;
 }
 
-// setInitialFrequency (demodulators.h:64): the product in float, the division
-// and round() in double.  A word outside +-4096 lets the reference's phase go
-// negative (phaseShift asserts, :109): refused.
+// setInitialFrequency (demodulators.h:64)
 SRCDSP_API int srcdsp_demod_set_initial_frequency(srcdsp_demod_t h, float f) {
-    const double w = std::round((double)(f * (float)4096) / kDemodPi);
-    SRCDSP_ARG_CHECK(w >= -4096.0 && w <= 4096.0, "demod_set_initial_frequency: frequency word outside +-4096");
+    int word = 0;
+    SRCDSP_ARG_CHECK(demod_freq_word(f, &word), "demod_set_initial_frequency: frequency word outside +-4096");
     SRCDSP_ARG_CHECK(h != nullptr, "demod_set_initial_frequency: null handle");
-    h->d.freq = (int)w;
+    h->d.freq = word;
     return SRCDSP_OK;
 }
 
@@ -428,13 +412,8 @@ SRCDSP_API int srcdsp_demod_step_batched(const srcdsp_demod_t *hs, int channels,
                                          size_t *n_soft, int32_t *error, void *stream) {
     SRCDSP_ARG_CHECK(hs != nullptr && n_soft != nullptr && error != nullptr && channels >= 1,
                      "demod_step_batched: no handles or result arrays");
-    for (int c = 0; c < channels; ++c) SRCDSP_ARG_CHECK(hs[c] != nullptr, "demod_step_batched: null handle");
-    {
-        std::vector<const void *> hv(hs, hs + channels);
-        std::sort(hv.begin(), hv.end());
-        SRCDSP_ARG_CHECK(std::adjacent_find(hv.begin(), hv.end()) == hv.end(),
-                         "demod_step_batched: every handle may be listed once");
-    }
+    int rc = check_handles(hs, channels, "demod_step_batched");
+    if (rc) return rc;
     if (n > 0x7fffffffUL) {
         set_error("demod_step_batched: input longer than INT_MAX samples (demodulators.cpp:181 uses int)");
         return SRCDSP_ERR_SIZE;
@@ -447,7 +426,7 @@ SRCDSP_API int srcdsp_demod_step_batched(const srcdsp_demod_t *hs, int channels,
         return SRCDSP_OK;
     }
     SRCDSP_ARG_CHECK(d_in != nullptr && d_soft != nullptr, "demod_step_batched: null buffer");
-    int rc = demod_check(hs, channels, n, "demod_step_batched");
+    rc = demod_check(hs, channels, n, "demod_step_batched");
     if (rc) return rc;
     for (int c = 0; c < channels; ++c)
         if (demod_n_soft(hs[c]->d, n) > soft_stride) {
@@ -524,22 +503,19 @@ SRCDSP_API int srcdsp_demod_acquire_batched(const srcdsp_demod_t *demods, const 
                          "demod_acquire_batched: first outside 0..N-1 of a correlator");
         taken.push_back(demods[c]);
     }
-    std::sort(taken.begin(), taken.end());
-    SRCDSP_ARG_CHECK(std::adjacent_find(taken.begin(), taken.end()) == taken.end(),
-                     "demod_acquire_batched: every demodulator may be listed once");
+    int rc = check_handle_list(taken, "demod_acquire_batched", "demodulator");
+    if (rc) return rc;
     std::vector<float> est((size_t)channels, 0.0f);
     std::vector<int> word((size_t)channels, 0);
     for (int c = 0; c < channels; ++c) {
         if (found && !found[c]) continue;
         srcdsp_corr_state &k = cors[c]->c;
-        int rc = k.order.sync();
+        rc = k.order.sync();
         if (rc) return rc;
         const FreqAcc a = freqest_row_host((const uint32_t *)k.bits.data() + first, k.N - (size_t)first, (size_t)L);
         est[c] = static_cast<float>(std::atan2((double)a.sq, (double)a.si) / L);
-        const float f = scale * est[c];
-        const double w = std::round((double)(f * (float)4096) / kDemodPi);
-        SRCDSP_ARG_CHECK(w >= -4096.0 && w <= 4096.0, "demod_acquire_batched: frequency word outside +-4096");
-        word[c] = (int)w;
+        SRCDSP_ARG_CHECK(demod_freq_word(scale * est[c], &word[c]),
+                         "demod_acquire_batched: frequency word outside +-4096");
     }
     for (int c = 0; c < channels; ++c) {
         if (found && !found[c]) continue;

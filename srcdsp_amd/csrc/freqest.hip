@@ -18,12 +18,9 @@ namespace srcdsp {
 struct FreqEst {
     int L = 1;
     int max_wg = 0;  // persistent workgroups of a launch: kFreqWgPerCu per compute unit, asked once
-    // grow-only scratch: slabs and result rows on the device, the rows' pinned
-    // mirror, the row offsets (pinned, and their device copy)
-    long long *d_slab = nullptr, *d_res = nullptr, *h_res = nullptr;
-    size_t slab_cap = 0, res_cap = 0;  // slabs, rows
-    long *d_off = nullptr, *h_off = nullptr;
-    size_t off_cap = 0;
+    // scratch: slabs on the device, result rows there and their pinned mirror,
+    // the row offsets (pinned, and their device copy)
+    GrowBuf slab{GrowBuf::kDevice}, res, off;
     HostStage stage;  // srcdsp_freqest_run_host
 };
 
@@ -34,35 +31,6 @@ int freqest_workgroups(int *out) {
     SRCDSP_HIP_TRY(hipGetDevice(&dev));
     SRCDSP_HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
     *out = kFreqWgPerCu * (cus > 0 ? cus : 1);
-    return SRCDSP_OK;
-}
-
-int freqest_reserve(FreqEst &f, size_t slabs, size_t rows, size_t offs) {
-    if (slabs > f.slab_cap) {
-        if (f.d_slab) (void)hipFree(f.d_slab);
-        f.d_slab = nullptr;
-        f.slab_cap = 0;
-        SRCDSP_HIP_TRY(hipMalloc(&f.d_slab, 8 * kFreqWords * slabs));
-        f.slab_cap = slabs;
-    }
-    if (rows > f.res_cap) {
-        if (f.d_res) (void)hipFree(f.d_res);
-        if (f.h_res) (void)hipHostFree(f.h_res);
-        f.d_res = f.h_res = nullptr;
-        f.res_cap = 0;
-        SRCDSP_HIP_TRY(hipMalloc(&f.d_res, 8 * kFreqWords * rows));
-        SRCDSP_HIP_TRY(hipHostMalloc(&f.h_res, 8 * kFreqWords * rows));
-        f.res_cap = rows;
-    }
-    if (offs > f.off_cap) {
-        if (f.d_off) (void)hipFree(f.d_off);
-        if (f.h_off) (void)hipHostFree(f.h_off);
-        f.d_off = f.h_off = nullptr;
-        f.off_cap = 0;
-        SRCDSP_HIP_TRY(hipMalloc(&f.d_off, 8 * offs));
-        SRCDSP_HIP_TRY(hipHostMalloc(&f.h_off, 8 * offs));
-        f.off_cap = offs;
-    }
     return SRCDSP_OK;
 }
 
@@ -93,25 +61,29 @@ int freqest_launch(FreqEst &f, int channels, const uint32_t *d_in, size_t in_str
         set_error("freqest: more workgroups than a launch takes");
         return SRCDSP_ERR_SIZE;
     }
-    int rc = freqest_reserve(f, bpr > 1 ? C * bpr : 0, C, in_offset ? C : 0);
+    int rc = f.slab.reserve(bpr > 1 ? 8 * kFreqWords * C * bpr : 0);
+    if (!rc) rc = f.res.reserve(8 * kFreqWords * C);
+    if (!rc) rc = f.off.reserve(in_offset ? 8 * C : 0);
     if (rc) return rc;
+    long long *d_slab = f.slab.dev<long long>(), *d_res = f.res.dev<long long>(), *h_res = f.res.host<long long>();
     if (in_offset) {
-        for (size_t c = 0; c < C; ++c) f.h_off[c] = (long)in_offset[c];
-        SRCDSP_HIP_TRY(hipMemcpyAsync(f.d_off, f.h_off, 8 * C, hipMemcpyHostToDevice, s));
+        long *h_off = f.off.host<long>();
+        for (size_t c = 0; c < C; ++c) h_off[c] = (long)in_offset[c];
+        SRCDSP_HIP_TRY(hipMemcpyAsync(f.off.d, h_off, 8 * C, hipMemcpyHostToDevice, s));
     }
     hipLaunchKernelGGL(freqest_rows, dim3((unsigned)(C * bpr)), dim3(kFreqLanes), 0, s, d_in, (long)in_stride,
-                       in_offset ? (const long *)f.d_off : nullptr, (long)n, (long)f.L, (int)bpr, (long)tiles_per_wg,
-                       f.d_slab, f.d_res);
+                       in_offset ? f.off.dev<const long>() : nullptr, (long)n, (long)f.L, (int)bpr, (long)tiles_per_wg,
+                       d_slab, d_res);
     SRCDSP_HIP_TRY(hipGetLastError());
     if (bpr > 1) {
-        hipLaunchKernelGGL(freqest_finish, dim3((unsigned)C), dim3(64), 0, s, (const long long *)f.d_slab, (int)bpr,
-                           f.d_res);
+        hipLaunchKernelGGL(freqest_finish, dim3((unsigned)C), dim3(64), 0, s, (const long long *)d_slab, (int)bpr,
+                           d_res);
         SRCDSP_HIP_TRY(hipGetLastError());
     }
-    SRCDSP_HIP_TRY(hipMemcpyAsync(f.h_res, f.d_res, 8 * kFreqWords * C, hipMemcpyDeviceToHost, s));
+    SRCDSP_HIP_TRY(hipMemcpyAsync(h_res, d_res, 8 * kFreqWords * C, hipMemcpyDeviceToHost, s));
     SRCDSP_HIP_TRY(hipStreamSynchronize(s));
     for (size_t c = 0; c < C; ++c)
-        freqest_result(f.h_res + kFreqWords * c, pairs, f.L, freq + c, sums ? sums + 2 * c : nullptr,
+        freqest_result(h_res + kFreqWords * c, pairs, f.L, freq + c, sums ? sums + 2 * c : nullptr,
                        exact ? exact + c : nullptr);
     return SRCDSP_OK;
 }
@@ -145,11 +117,9 @@ SRCDSP_API int srcdsp_freqest_create(srcdsp_freqest_t *out, int L) {
 SRCDSP_API int srcdsp_freqest_destroy(srcdsp_freqest_t h) {
     if (!h) return SRCDSP_OK;
     FreqEst &f = h->f;
-    if (f.d_slab) (void)hipFree(f.d_slab);
-    if (f.d_res) (void)hipFree(f.d_res);
-    if (f.h_res) (void)hipHostFree(f.h_res);
-    if (f.d_off) (void)hipFree(f.d_off);
-    if (f.h_off) (void)hipHostFree(f.h_off);
+    f.slab.destroy();
+    f.res.destroy();
+    f.off.destroy();
     if (f.stage.stream) f.stage.destroy();
     delete h;
     return SRCDSP_OK;

@@ -98,8 +98,7 @@ static int mixer_launch(MixerState &m, const void *d_in, size_t n, void *d_out, 
                            (uint32_t *)d_out, (unsigned long)n, m.d_table, N, phi, fr);
     }
     SRCDSP_HIP_TRY(hipGetLastError());
-    // phi after n samples: (phi + n*freq) mod N  (mixers.h:177 iterated)
-    m.phi = (int16_t)(((unsigned long)phi + (unsigned long)(n % N) * fr) % N);
+    m.advance(n);
     return m.order.after(s);
 }
 
@@ -145,7 +144,7 @@ SRCDSP_API int srcdsp_mixer_destroy(srcdsp_mixer_t h) {
     if (!h) return SRCDSP_OK;
     (void)h->m.order.sync();
     if (h->m.d_table) (void)hipFree(h->m.d_table);
-    if (h->m.d_scratch) (void)hipFree(h->m.d_scratch);
+    h->m.scratch.destroy();
     delete[] h->m.h_table;
     h->m.order.destroy();
     h->m.stage.destroy();

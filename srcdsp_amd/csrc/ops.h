@@ -87,12 +87,18 @@ struct MixerState {
     float nominal = 0.f;
     int16_t *d_table = nullptr;
     int16_t *h_table = nullptr;
-    // grow-only scratch of the unfused mixer -> decimator chain (the mixed
-    // samples between the two launches)
-    void *d_scratch = nullptr;
-    size_t scratch_cap = 0;
+    // scratch of the unfused mixer -> decimator chain (the mixed samples
+    // between the two launches)
+    GrowBuf scratch{GrowBuf::kDevice};
     Ordering order;
     HostStage stage;
+
+    // phase after n more samples: phi += n * freq (mod N), mixers.h:177 iterated
+    void advance(unsigned long n) {
+        phi = (int16_t)(((unsigned long)(unsigned)phi + (unsigned long)(n % N) * (unsigned)freq) % N);
+    }
+    // the bank kernels' per-channel mixer word: lo phase, hi frequency word
+    uint32_t word() const { return (uint32_t)(uint16_t)phi | ((uint32_t)(uint16_t)freq << 16); }
 };
 
 }  // namespace srcdsp

@@ -1,7 +1,8 @@
 // runtime.hip -- host-side runtime pieces shared by every operator of
 // libsrcdsp_hip.so: error reporting, the coefficient-scaling semantics of the
-// reference constructors, stream ordering, pinned staging, and the synthetic
-// sample generator used by benchmarks.
+// reference constructors, stream ordering, pinned staging, the batched entry
+// points' shared frame (bank_host.h), and the synthetic sample generator used
+// by benchmarks.
 #include "common.h"
 
 #include <algorithm>
@@ -169,27 +170,41 @@ int HostStage::init() {
     return SRCDSP_OK;
 }
 int HostStage::reserve(size_t hb, size_t db) {
-    if (hb > h_cap) {
-        if (h_buf) (void)hipHostFree(h_buf);
-        h_buf = nullptr;
-        SRCDSP_HIP_TRY(hipHostMalloc(&h_buf, hb, hipHostMallocDefault));
-        h_cap = hb;
-    }
-    if (db > d_cap) {
-        if (d_buf) (void)hipFree(d_buf);
-        d_buf = nullptr;
-        SRCDSP_HIP_TRY(hipMalloc(&d_buf, db));
-        d_cap = db;
-    }
-    return SRCDSP_OK;
+    int rc = pinned.reserve(hb);
+    if (!rc) rc = device.reserve(db);
+    h_buf = pinned.h;
+    d_buf = device.d;
+    return rc;
 }
 void HostStage::destroy() {
-    if (h_buf) (void)hipHostFree(h_buf);
-    if (d_buf) (void)hipFree(d_buf);
+    pinned.destroy();
+    device.destroy();
     if (stream) (void)hipStreamDestroy(stream);
     h_buf = d_buf = nullptr;
     stream = nullptr;
-    h_cap = d_cap = 0;
+}
+
+int check_handle_list(std::vector<const void *> &hv, const char *who, const char *what) {
+    for (const void *h : hv) SRCDSP_ARG_CHECK(h != nullptr, std::string(who) + ": null handle");
+    std::sort(hv.begin(), hv.end());
+    SRCDSP_ARG_CHECK(std::adjacent_find(hv.begin(), hv.end()) == hv.end(),
+                     std::string(who) + ": every " + what + " may be listed once");
+    return SRCDSP_OK;
+}
+
+int GrowBuf::reserve(size_t bytes) {
+    if (bytes <= cap) return SRCDSP_OK;
+    destroy();
+    if (kind & kDevice) SRCDSP_HIP_TRY(hipMalloc(&d, bytes));
+    if (kind & kPinned) SRCDSP_HIP_TRY(hipHostMalloc(&h, bytes, hipHostMallocDefault));
+    cap = bytes;
+    return SRCDSP_OK;
+}
+void GrowBuf::destroy() {
+    if (d) (void)hipFree(d);
+    if (h) (void)hipHostFree(h);
+    d = h = nullptr;
+    cap = 0;
 }
 
 int sample_bytes(int kind) {

@@ -22,8 +22,6 @@
 // the bank then loops over its channels.  Either way outputs and both handles'
 // state are those of the two calls, bit for bit.
 #include <algorithm>
-#include <atomic>
-#include <vector>
 
 #include "ops.h"
 
@@ -32,7 +30,7 @@
 
 namespace srcdsp {
 namespace {
-std::atomic<unsigned long> g_fused_calls{0}, g_pair_calls{0}, g_bank_calls{0}, g_loop_calls{0};
+PathCounter g_fused_calls, g_pair_calls, g_bank_calls, g_loop_calls;
 
 constexpr unsigned kUpmixMaxN = 4096;  // table entries staged in LDS (8 KiB)
 
@@ -109,14 +107,11 @@ int fused_launch(const srcdsp_up_t *ups, const srcdsp_mixer_t *mixers, int nc, c
     P.tab_off = (unsigned)tile_lds;
     const size_t smem = tile_lds + ((2 * (size_t)P.N + 15) & ~(size_t)15);
     for (int c = 0; c < nc; ++c) {
-        srcdsp_up_state &u = ups[c]->u;
         MixerState &m = mixers[c]->m;
-        int rc = u.order.before(s);
+        int rc = chan_begin(ups[c]->u, s, P.hist_in[c], P.hist_out[c]);
         if (!rc) rc = m.order.before(s);
         if (rc) return rc;
-        P.hist_in[c] = (const uint32_t *)u.d_hist[u.cur];
-        P.hist_out[c] = (uint32_t *)u.d_hist[u.cur ^ 1];
-        P.mix[c] = (uint32_t)(uint16_t)m.phi | ((uint32_t)(uint16_t)m.freq << 16);
+        P.mix[c] = m.word();
     }
     constexpr int TI = kUpRD * kUpBlockD;
     const int PP = (u0.H + 1) / 2;
@@ -149,12 +144,9 @@ int fused_launch(const srcdsp_up_t *ups, const srcdsp_mixer_t *mixers, int nc, c
     SRCDSP_HIP_TRY(hipGetLastError());
     const unsigned long n_out = (unsigned long)u0.L * (unsigned long)n_total;
     for (int c = 0; c < nc; ++c) {
-        srcdsp_up_state &u = ups[c]->u;
         MixerState &m = mixers[c]->m;
-        u.cur ^= 1;
-        // mixer phase after the call: phi += n_out * freq (mod N), mixers.h:177
-        m.phi = (int16_t)(((unsigned long)(unsigned)m.phi + (n_out % m.N) * (unsigned)m.freq) % m.N);
-        int rc = u.order.after(s);
+        m.advance(n_out);
+        int rc = chan_commit(ups[c]->u, s);
         if (!rc) rc = m.order.after(s);
         if (rc) return rc;
     }
@@ -200,7 +192,7 @@ SRCDSP_API int srcdsp_upmix_step(srcdsp_up_t up, srcdsp_mixer_t mixer, const voi
     const bool ran = n_out != 0;
     bool fused = false;
     int rc = upmix_one(up, mixer, d_in, n_in, d_out, n_out, flush != 0, iterator != 0, stream, &fused);
-    if (rc == SRCDSP_OK && ran) (fused ? g_fused_calls : g_pair_calls).fetch_add(1, std::memory_order_relaxed);
+    if (rc == SRCDSP_OK && ran) (fused ? g_fused_calls : g_pair_calls).hit();
     return rc;
 }
 
@@ -208,8 +200,9 @@ SRCDSP_API int srcdsp_upmix_step_batched(const srcdsp_up_t *ups, const srcdsp_mi
                                          const void *d_in, size_t in_stride, void *d_out, size_t out_stride,
                                          size_t n_in, int flush, void *stream) {
     SRCDSP_ARG_CHECK(ups != nullptr && mixers != nullptr && channels >= 1, "upmix_step_batched: no handles");
-    for (int c = 0; c < channels; ++c)
-        SRCDSP_ARG_CHECK(ups[c] != nullptr && mixers[c] != nullptr, "upmix_step_batched: null handle");
+    int rc = check_handles(ups, channels, "upmix_step_batched");
+    if (!rc) rc = check_handles(mixers, channels, "upmix_step_batched");
+    if (rc) return rc;
     const srcdsp_up_state &u0 = ups[0]->u;
     const MixerState &m0 = mixers[0]->m;
     if (u0.variant == UV_I16_I32) {
@@ -222,14 +215,6 @@ SRCDSP_API int srcdsp_upmix_step_batched(const srcdsp_up_t *ups, const srcdsp_mi
                          "upmix_step_batched: interpolators must share variant, L and taps");
         SRCDSP_ARG_CHECK(mixers[c]->m.N == m0.N, "upmix_step_batched: mixers must share N");
     }
-    {
-        std::vector<const void *> hu(ups, ups + channels), hm(mixers, mixers + channels);
-        std::sort(hu.begin(), hu.end());
-        std::sort(hm.begin(), hm.end());
-        SRCDSP_ARG_CHECK(std::adjacent_find(hu.begin(), hu.end()) == hu.end() &&
-                             std::adjacent_find(hm.begin(), hm.end()) == hm.end(),
-                         "upmix_step_batched: every handle may be listed once");
-    }
     const size_t extra = flush ? u0.length / u0.L : 0;
     const size_t n_out = (size_t)u0.L * (n_in + extra);
     SRCDSP_ARG_CHECK(in_stride == 0 || in_stride >= n_in, "upmix_step_batched: in_stride must be 0 (shared) or >= n_in");
@@ -240,32 +225,28 @@ SRCDSP_API int srcdsp_upmix_step_batched(const srcdsp_up_t *ups, const srcdsp_mi
     if (n_out == 0) return SRCDSP_OK;
     SRCDSP_ARG_CHECK(d_out && (d_in || n_in == 0), "upmix_step_batched: null buffer");
     if (!(fused_takes(u0, m0, d_in, d_out) && (in_stride * 4) % 16 == 0 && (out_stride * 4) % 16 == 0)) {
-        g_loop_calls.fetch_add(1, std::memory_order_relaxed);
-        for (int c = 0; c < channels; ++c) {
+        g_loop_calls.hit();
+        for (int c = 0; c < channels && !rc; ++c) {
             bool fused;
-            int rc = upmix_one(ups[c], mixers[c], (const char *)d_in + (size_t)c * in_stride * 4, n_in,
-                               (char *)d_out + (size_t)c * out_stride * 4, n_out, flush != 0, false, stream, &fused);
-            if (rc) return rc;
+            rc = upmix_one(ups[c], mixers[c], chan_row(d_in, c, in_stride), n_in, chan_row(d_out, c, out_stride), n_out,
+                           flush != 0, false, stream, &fused);
         }
-        return SRCDSP_OK;
+        return rc;
     }
-    g_bank_calls.fetch_add(1, std::memory_order_relaxed);
-    for (int c0 = 0; c0 < channels; c0 += kMaxBatch) {
-        const int nc = std::min(kMaxBatch, channels - c0);
-        int rc = fused_launch(ups + c0, mixers + c0, nc, (const char *)d_in + (size_t)c0 * in_stride * 4, in_stride,
-                              (char *)d_out + (size_t)c0 * out_stride * 4, out_stride, n_in, (long)(n_in + extra),
-                              false, (hipStream_t)stream);
-        if (rc) return rc;
-    }
-    return SRCDSP_OK;
+    g_bank_calls.hit();
+    for (int c0 = 0; c0 < channels && !rc; c0 += kMaxBatch)
+        rc = fused_launch(ups + c0, mixers + c0, std::min(kMaxBatch, channels - c0), chan_row(d_in, c0, in_stride),
+                          in_stride, chan_row(d_out, c0, out_stride), out_stride, n_in, (long)(n_in + extra), false,
+                          (hipStream_t)stream);
+    return rc;
 }
 
 SRCDSP_API int srcdsp_upmix_stats(unsigned long *fused_calls, unsigned long *pair_calls, unsigned long *bank_calls,
                                   unsigned long *loop_calls) {
-    if (fused_calls) *fused_calls = g_fused_calls.load(std::memory_order_relaxed);
-    if (pair_calls) *pair_calls = g_pair_calls.load(std::memory_order_relaxed);
-    if (bank_calls) *bank_calls = g_bank_calls.load(std::memory_order_relaxed);
-    if (loop_calls) *loop_calls = g_loop_calls.load(std::memory_order_relaxed);
+    g_fused_calls.read(fused_calls);
+    g_pair_calls.read(pair_calls);
+    g_bank_calls.read(bank_calls);
+    g_loop_calls.read(loop_calls);
     return SRCDSP_OK;
 }
 

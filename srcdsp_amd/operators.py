@@ -93,6 +93,11 @@ def _stream(x):
     return C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
 
 
+def _handles(objs):
+    """The C array of the objects' handles, as the *_batched calls take it."""
+    return (C.c_void_p * len(objs))(*[o._h.value for o in objs])
+
+
 def _coeffs(c, kind: str) -> np.ndarray:
     return np.ascontiguousarray(c, _NP[kind])
 
@@ -194,7 +199,7 @@ class FilterDnsamplingFir(_Handle):
 def decim_step_batched(filters, inp, out):
     """Step C same-configuration decimators over a [C, L] device batch in one
     launch (grid.y = channel)."""
-    hs = (C.c_void_p * len(filters))(*[f._h.value for f in filters])
+    hs = _handles(filters)
     f0 = filters[0]
     ch = len(filters)
     n_in = _nsamples(inp, f0.kin) // ch
@@ -409,8 +414,8 @@ def mixdecim_step_batched(mixers, decims, inp, out):
     M = decims[0].M
     if out.shape[0] != ch or out.shape[1] * M != n_in:
         raise ValueError("DDC bank: out must be [C, L // M] with L a multiple of M")
-    hm = (C.c_void_p * ch)(*[m._h.value for m in mixers])
-    hd = (C.c_void_p * ch)(*[d._h.value for d in decims])
+    hm = _handles(mixers)
+    hd = _handles(decims)
     A.call("srcdsp_mixdecim_step_batched", hm, hd, ch, _ptr(inp), 0 if shared else n_in, _ptr(out), out.shape[1],
            n_in, _stream(inp))
     return out
@@ -462,8 +467,8 @@ def upmix_step_batched(ups, mixers, inp, out, flush: bool = False):
     if (not shared and inp.shape[0] != ch) or out.shape[0] != ch:
         raise ValueError("upmix bank: one input row (or one shared input) and one output row per channel")
     n_in = inp.shape[-2]
-    hu = (C.c_void_p * ch)(*[u._h.value for u in ups])
-    hm = (C.c_void_p * ch)(*[m._h.value for m in mixers])
+    hu = _handles(ups)
+    hm = _handles(mixers)
     A.call("srcdsp_upmix_step_batched", hu, hm, ch, _ptr(inp), 0 if shared else n_in, _ptr(out), out.shape[1],
            n_in, int(flush), _stream(inp))
     return out
@@ -577,7 +582,7 @@ def corr_step_batched(correlators, inp):
     if not shared and inp.shape[0] != ch:
         raise ValueError("corr_step_batched: one input row per correlator")
     n = inp.shape[-2]
-    hs = (C.c_void_p * ch)(*[c._h.value for c in correlators])
+    hs = _handles(correlators)
     found, idx = (C.c_int * ch)(), (C.c_int * ch)(*([-1] * ch))
     A.call("srcdsp_corr_step_batched", hs, ch, _ptr(inp), 0 if shared else n, n, found, idx, _stream(inp))
     return [(bool(found[c]), idx[c]) for c in range(ch)]
@@ -700,7 +705,7 @@ def demod_step_batched(demods, x, offsets=None, n=None):
         n = m - max(offs)
     if n < 0 or max(offs) + n > m:
         raise ValueError("demod_step_batched: offset + n runs past the row")
-    hs = (C.c_void_p * ch)(*[d._h.value for d in demods])
+    hs = _handles(demods)
     off = (C.c_size_t * ch)(*offs)
     ns, err = (C.c_size_t * ch)(), (C.c_int32 * ch)()
     soft = torch.empty((ch, max(n, 1)), dtype=torch.int8, device=x.device)
@@ -799,8 +804,8 @@ def demod_acquire_batched(demods, cors, found=None, L=1, first=1, scale=-1.0):
         raise ValueError("demod_acquire_batched: one correlator per demodulator, at least one")
     if found is not None and len(found) != ch:
         raise ValueError("demod_acquire_batched: one found flag per channel")
-    hd = (C.c_void_p * ch)(*[d._h.value for d in demods])
-    hc = (C.c_void_p * ch)(*[c._h.value for c in cors])
+    hd = _handles(demods)
+    hc = _handles(cors)
     fl = None if found is None else (C.c_int * ch)(*[int(bool(v)) for v in found])
     f = np.full(ch, np.nan, np.float32)
     A.call("srcdsp_demod_acquire_batched", hd, hc, ch, fl, int(L), int(first), C.c_float(scale),

@@ -70,6 +70,26 @@ def test_argument_errors_need_no_gpu(capi):
     assert lib.srcdsp_fill_synthetic(None, 0, 5, 0, 0, 0, 0, 1, None) == capi.ERR_ARG
 
 
+def test_batched_entry_points_refuse_a_null_handle_alike(capi):
+    """The handle-list check the *_batched calls share: a null entry is
+    ERR_ARG with the entry point's own name in front, before any HIP call."""
+    import ctypes as C
+    lib = capi.lib()
+    hs, hs2 = (C.c_void_p * 2)(None, None), (C.c_void_p * 2)(None, None)
+    found, idx = (C.c_int * 2)(), (C.c_int * 2)()
+    ns, err = (C.c_size_t * 2)(), (C.c_int32 * 2)()
+    calls = {
+        "decim_step_batched": lambda: lib.srcdsp_decim_step_batched(hs, 2, None, 0, None, 0, 0, None),
+        "mixdecim_step_batched": lambda: lib.srcdsp_mixdecim_step_batched(hs, hs2, 2, None, 0, None, 0, 0, None),
+        "upmix_step_batched": lambda: lib.srcdsp_upmix_step_batched(hs, hs2, 2, None, 0, None, 0, 0, 0, None),
+        "corr_step_batched": lambda: lib.srcdsp_corr_step_batched(hs, 2, None, 0, 0, found, idx, None),
+        "demod_step_batched": lambda: lib.srcdsp_demod_step_batched(hs, 2, None, 0, None, 0, None, 0, ns, err, None),
+    }
+    for name, call in calls.items():
+        assert call() == capi.ERR_ARG, name
+        assert lib.srcdsp_last_error() == (name + ": null handle").encode(), name
+
+
 def test_library_does_not_link_rccl(capi):
     """RCCL is dlopened by srcdsp_comm_create only (multi.hip), so single-GPU
     users neither link nor load it: no DT_NEEDED entry for librccl."""

@@ -279,6 +279,32 @@ def test_past_the_batch_limit(S, O):
         assert events[c][:1] == ([(0, TILE + 19)] if c % 8 == 0 else []), (c, events[c])
 
 
+def test_lead_scratch_grows_and_is_reused(S, O):
+    """The bank's scratch lives on hs[0] and only grows: one lead through calls
+    of 2, 5 and 2 channels (kept, regrown, reused at the larger capacity), each
+    call against single-channel steps on clones; a burst in the last channel of
+    every call, so its bitSamples row is copied back."""
+    import copy
+    N, n = 64, 2048
+    ps = [pattern(N, 40 + c) for c in range(5)]
+    cors, _ = make(S, O, ps, N)
+    b0, l0 = S.corr_batched_stats()
+    for call, ch in enumerate((2, 5, 2)):
+        x = np.stack([signal(n, 900 + 10 * call + c, [(700 + call, ps[c])] if c == ch - 1 else []) for c in range(ch)])
+        twins = [copy.copy(g) for g in cors[:ch]]
+        xd = dev(x)
+        got = S.corr_step_batched(cors[:ch], xd)
+        assert [f for f, _ in got] == [c == ch - 1 for c in range(ch)], (call, got)
+        assert got[ch - 1][1] == 700 + call + N - 1, (call, got)
+        for c in range(ch):
+            want = twins[c].step(xd[c])
+            assert (got[c][0], got[c][0] and got[c][1]) == (want[0], want[0] and want[1]), (call, c, got[c], want)
+            assert cors[c].getStatus() == twins[c].getStatus(), (call, c)
+            assert np.array_equal(cors[c].getRefBitSamples(), twins[c].getRefBitSamples()), (call, c)
+    b1, l1 = S.corr_batched_stats()
+    assert (b1 - b0, l1 - l0) == (3, 0)
+
+
 # ------------------------------------------------------------ 7. hand-over
 def test_state_equals_single_channel_api_and_hands_over(S, O):
     import copy

@@ -230,6 +230,27 @@ def test_bank_and_single_steps_continue_each_other(S):
     bank(2 * N_BANK, 3 * N_BANK)
 
 
+def test_lead_scratch_grows_and_is_reused(S):
+    """The table and the result rows live on hs[0] and only grow: one lead
+    through calls of 2, 5 and 2 channels (kept, regrown, reused at the larger
+    capacity), each call against the loop of single steps on clones."""
+    import copy
+    gs = [pair(S, 32, c % 3, (13, -13, 500, 0, -777)[c], 600 + c)[0] for c in range(5)]
+    for call, ch in enumerate((2, 5, 2)):
+        xd = dev(noise(20 + call, (ch, 512)))
+        loop = [copy.copy(g) for g in gs[:ch]]
+        soft, ns, errs = S.demod_step_batched(gs[:ch], xd)
+        soft = soft.cpu().numpy()
+        for c in range(ch):
+            ls, lerr = loop[c].step(xd[c])
+            first = call == (0 if c < 2 else 1)  # a handle's first call keeps the 32 preamble bits back
+            assert ns[c] == len(ls) == (512 - 32 if first else 512), (call, c)
+            assert np.array_equal(soft[c, :ns[c]], ls.cpu().numpy()) and errs[c] == lerr, (call, c)
+            assert gs[c].state() == loop[c].state(), (call, c)
+            assert np.float32(gs[c].getMeasuredFrequency()).tobytes() == \
+                np.float32(loop[c].getMeasuredFrequency()).tobytes(), (call, c)
+
+
 def test_refusals_change_no_handle(S):
     from srcdsp_amd import _capi as A
     lib = A.lib()

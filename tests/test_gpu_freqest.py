@@ -200,6 +200,26 @@ def test_bank_after_a_longer_call_and_below_L(S, noise):
         assert [M.bits(v) for v in f] == [0] * 3 and not sums.any() and exact.all()
 
 
+def test_bank_scratch_grows_and_is_reused(S, noise):
+    """The result rows and the row offsets live on the handle and only grow: one
+    handle through calls of 2, 5 and 2 rows with offsets (kept, regrown, reused
+    at the larger capacity), each row against the single-row call of a second
+    handle (a handle has no signal state to clone) and the model."""
+    x, xd = noise
+    L, n = 1, 1024
+    e, one = S.FreqEstimator(L), S.FreqEstimator(L)
+    for call, ch in enumerate((2, 5, 2)):
+        base = call * 5 * (n + 8)
+        rows = xd[base:base + ch * (n + 8)].reshape(ch, n + 8, 2)
+        offs = [1 + (c + call) % 7 for c in range(ch)]
+        f, sums, exact = e.run_batched(rows, offsets=offs, n=n)
+        for c in range(ch):
+            lo = base + c * (n + 8) + offs[c]
+            f1, s1, e1 = one.run(xd[lo:lo + n])
+            assert (M.bits(f[c]), tuple(int(v) for v in sums[c]), bool(exact[c])) == (M.bits(f1), s1, e1), (call, c)
+            check((f[c], sums[c], exact[c]), x[lo:lo + n], L, (call, c))
+
+
 def test_run_host_equals_run(S, noise, geo):
     x, xd = noise
     T, W, G = geo

@@ -610,6 +610,39 @@ def test_decim_errors_and_empty(S):
         d2.setCoeffs(np.ones(7, np.float32))  # dsptl_dnsampling_filters.h:122 assert
 
 
+def test_decim_batched_refuses_null_and_repeated_handles(S, O):
+    """A handle listed twice, or a null handle in the list: ERR_ARG before
+    anything is enqueued -- both histories stay as the step before left them,
+    and the next valid batched step continues the oracle's stream."""
+    import ctypes as C
+    import torch
+    from srcdsp_amd import _capi as A
+    from srcdsp_amd.design import hamming_sinc
+    c, M, L = hamming_sinc(31), 4, 4096
+    x = np.stack([O["fma"].gen_cf32(0x5EED, ch, 0, 2 * L) for ch in range(2)])
+    fs = [S.FilterDnsamplingFir(c, M) for _ in range(2)]
+    refs = [O["fma"].decim(0, M, c) for _ in range(2)]
+    out = torch.empty((2, L // M), dtype=torch.complex64, device="cuda")
+    S.decim_step_batched(fs, dev(x[:, :L]), out)
+    for ch in range(2):
+        assert np.array_equal(out[ch].cpu().numpy(), refs[ch].step(x[ch, :L])), ch
+    hist = [f.state()["history"].copy() for f in fs]
+    assert all(h.any() for h in hist)
+    xd = dev(x[:, L:])
+    with pytest.raises(A.SrcdspError) as e:
+        S.decim_step_batched([fs[0], fs[0]], xd, out)
+    assert e.value.code == A.ERR_ARG and "listed once" in str(e.value)
+    hs = (C.c_void_p * 2)(fs[0]._h.value, None)
+    with pytest.raises(A.SrcdspError) as e:
+        A.call("srcdsp_decim_step_batched", hs, 2, xd.data_ptr(), L, out.data_ptr(), L // M, L, None)
+    assert e.value.code == A.ERR_ARG and "null handle" in str(e.value)
+    for f, h in zip(fs, hist):
+        assert np.array_equal(f.state()["history"], h)
+    S.decim_step_batched(fs, xd, out)
+    for ch in range(2):
+        assert np.array_equal(out[ch].cpu().numpy(), refs[ch].step(x[ch, L:])), ch
+
+
 def test_headline_whole_output(S, O):
     """Config 2 at full size (2^28 complex<float> samples, device-resident, one
     step()), both float contracts: EVERY one of the 2^26 outputs
