@@ -246,6 +246,89 @@ SRCDSP_API int srcdsp_upmix_stats(unsigned long *fused_calls, unsigned long *pai
                                   unsigned long *bank_calls, unsigned long *loop_calls);
 
 /* ============================================================================
+ * SymbolMapperSdpsk<int16_t> (modulators.h:82-131) and
+ * SymbolMapperQpsk<int16_t>  (modulators.h:147-198)
+ * A bit is a uint8_t and a one whenever it is non-zero (`bits[i] > 0`, :110,
+ * :177).  A symbol is complex<int16_t> of amplitude 8192 (:34-39).
+ * ==========================================================================*/
+typedef struct srcdsp_mapper *srcdsp_mapper_t;
+#define SRCDSP_MAPPER_SDPSK 0
+#define SRCDSP_MAPPER_QPSK 1
+
+/* the constructors (modulators.h:87-99, :152-165); state 0.  No device call: a
+ * handle is a host object until it steps on device buffers. */
+SRCDSP_API int srcdsp_mapper_create(srcdsp_mapper_t *out, int kind);
+SRCDSP_API int srcdsp_mapper_destroy(srcdsp_mapper_t h);
+/* the implicit copy constructor: kind and state (waits for the last step) */
+SRCDSP_API int srcdsp_mapper_clone(srcdsp_mapper_t h, srcdsp_mapper_t *out);
+/* reset() (modulators.h:120-123, :187-190): state 0 */
+SRCDSP_API int srcdsp_mapper_reset(srcdsp_mapper_t h);
+/* the private `state` member (modulators.h:127, :194); waits for the handle's
+ * last step */
+SRCDSP_API int srcdsp_mapper_get_state(srcdsp_mapper_t h, int *kind, int *state);
+/* Extension (no reference call): set the state, 0..3, so that a bit stream can
+ * be split in time (as srcdsp_mixer_set_phase does for the mixer). */
+SRCDSP_API int srcdsp_mapper_set_state(srcdsp_mapper_t h, int state);
+/* the bits one workgroup tile of the kernels covers */
+SRCDSP_API int srcdsp_mapper_geometry(int *tile_bits);
+/* step() (modulators.h:103-117 SDPSK: state = (state + (bit ? 1 : 3)) % 4 per
+ * bit, out[i] = map[state], n_out == n_bits; :169-184 QPSK: state = first bit
+ * << 1 | second bit per pair, n_bits == 2 n_out) on device buffers: d_bits
+ * uint8_t[n_bits], d_out complex<int16_t>[n_out].  The reference's asserts on
+ * the sizes (:106, :171) are SRCDSP_ERR_SIZE; n_bits == 0 changes nothing. */
+SRCDSP_API int srcdsp_mapper_step(srcdsp_mapper_t h, const void *d_bits, size_t n_bits, void *d_out, size_t n_out,
+                                  void *stream);
+SRCDSP_API int srcdsp_mapper_step_host(srcdsp_mapper_t h, const void *bits, size_t n_bits, void *out, size_t n_out);
+/* Extension (no reference call).  C mappers in one call: row c reads d_bits +
+ * c*bits_stride bytes and writes d_out + c*out_stride samples exactly as
+ * srcdsp_mapper_step(hs[c], ...) (modulators.h:103-117, :169-184) would.
+ * bits_stride == 0: every row reads the SAME bits; otherwise bits_stride >=
+ * n_bits.  out_stride >= the row's symbols (SRCDSP_ERR_SIZE otherwise, as an
+ * odd QPSK n_bits).  The mappers share a kind (their states may differ), every
+ * handle is listed once, channels >= 1 (SRCDSP_ERR_ARG otherwise).  A refused
+ * call changes no handle. */
+SRCDSP_API int srcdsp_mapper_step_batched(const srcdsp_mapper_t *hs, int channels, const void *d_bits,
+                                          size_t bits_stride, void *d_out, size_t out_stride, size_t n_bits,
+                                          void *stream);
+
+/* Mapper -> FilterUpsamplingFir (variant 0 or 1) -> Mixer, the transmit chain
+ * from bits: the three reference calls mapper.step(bits, sym)
+ * (modulators.h:103-117 / :169-184); up.step(sym, tmp, flush)
+ * (upsampling_filters.h:149-233; iterator=1: :240-323); mixer.step(tmp, out)
+ * (mixers.h:169-188) in one call.  n_out follows srcdsp_upmix_step with n_in
+ * the symbol count (n_bits, or n_bits / 2 for QPSK; an odd QPSK n_bits is
+ * SRCDSP_ERR_SIZE).  All three handles advance as in the three calls: the
+ * interpolator's history ends holding the last symbols, the mixer advances by
+ * n_out, the mapper reaches its end state; a later single-operator call on any
+ * of them continues bit for bit.  A real int16_t interpolator is
+ * SRCDSP_ERR_UNSUPPORTED.  A refused call changes no handle.
+ * One kernel (the interpolator's tile fed from bits, the mixer in its
+ * epilogue) serves what srcdsp_upmix_step's kernel serves when d_bits is
+ * 16-byte aligned too; every other shape runs srcdsp_mapper_step into scratch
+ * and srcdsp_upmix_step inside the call. */
+SRCDSP_API int srcdsp_modulate_step(srcdsp_mapper_t mapper, srcdsp_up_t up, srcdsp_mixer_t mixer, const void *d_bits,
+                                    size_t n_bits, void *d_out, size_t n_out, int flush, int iterator, void *stream);
+/* Extension (no reference call).  C such chains in one call: row c is
+ * srcdsp_modulate_step(mappers[c], ups[c], mixers[c], d_bits + c*bits_stride
+ * bytes, ..., d_out + c*out_stride samples, ...) (modulators.h:103-117 /
+ * :169-184, upsampling_filters.h:149-233, mixers.h:169-188).  bits_stride == 0:
+ * shared bits; otherwise >= n_bits.  out_stride as srcdsp_upmix_step_batched.
+ * The mappers share a kind, the interpolators variant, L and taps, the mixers
+ * N; every handle is listed once (SRCDSP_ERR_ARG otherwise).  One launch
+ * serves the single call's kernel shapes when the row strides are multiples
+ * of 16 bytes; every other shape loops over the channels. */
+SRCDSP_API int srcdsp_modulate_step_batched(const srcdsp_mapper_t *mappers, const srcdsp_up_t *ups,
+                                            const srcdsp_mixer_t *mixers, int channels, const void *d_bits,
+                                            size_t bits_stride, void *d_out, size_t out_stride, size_t n_bits,
+                                            int flush, void *stream);
+/* process-wide counters (the paths of modulators.h:103-184 ->
+ * upsampling_filters.h:149-233 -> mixers.h:169-188): single calls served by
+ * the fused kernel / by the mapper then srcdsp_upmix_step, batched calls
+ * served by one launch / by the per-channel loop */
+SRCDSP_API int srcdsp_modulate_stats(unsigned long *fused_calls, unsigned long *chain_calls,
+                                     unsigned long *bank_calls, unsigned long *loop_calls);
+
+/* ============================================================================
  * FixedPatternCorrelator<int16_t, int32_t, N, S>   (correlators.h:54-316)
  * ==========================================================================*/
 typedef struct srcdsp_corr *srcdsp_corr_t;

@@ -66,6 +66,19 @@ SIGNATURES = {
     "srcdsp_upmix_step": (I, [VP, VP, VP, SZ, VP, SZ, I, I, VP]),
     "srcdsp_upmix_step_batched": (I, [HP, HP, I, VP, SZ, VP, SZ, SZ, I, VP]),
     "srcdsp_upmix_stats": (I, [C.POINTER(C.c_ulong)] * 4),
+    "srcdsp_mapper_create": (I, [HP, I]),
+    "srcdsp_mapper_destroy": (I, [VP]),
+    "srcdsp_mapper_clone": (I, [VP, HP]),
+    "srcdsp_mapper_reset": (I, [VP]),
+    "srcdsp_mapper_get_state": (I, [VP, IP, IP]),
+    "srcdsp_mapper_set_state": (I, [VP, I]),
+    "srcdsp_mapper_geometry": (I, [IP]),
+    "srcdsp_mapper_step": (I, [VP, VP, SZ, VP, SZ, VP]),
+    "srcdsp_mapper_step_host": (I, [VP, VP, SZ, VP, SZ]),
+    "srcdsp_mapper_step_batched": (I, [HP, I, VP, SZ, VP, SZ, SZ, VP]),
+    "srcdsp_modulate_step": (I, [VP, VP, VP, VP, SZ, VP, SZ, I, I, VP]),
+    "srcdsp_modulate_step_batched": (I, [HP, HP, HP, I, VP, SZ, VP, SZ, SZ, I, VP]),
+    "srcdsp_modulate_stats": (I, [C.POINTER(C.c_ulong)] * 4),
     "srcdsp_corr_create": (I, [HP, U, U]),
     "srcdsp_corr_destroy": (I, [VP]),
     "srcdsp_corr_clone": (I, [VP, HP]),

@@ -1,0 +1,307 @@
+// modulate.hip -- SymbolMapper{Sdpsk,Qpsk} -> FilterUpsamplingFir -> Mixer in
+// one call (the transmit chain from bits: modulators.h:103-117 / :169-184,
+// upsampling_filters.h:149-233, mixers.h:169-188), single
+// (srcdsp_modulate_step) and as a bank of C chains (srcdsp_modulate_step_batched).
+//
+// The kernel is the interpolator's v_dot2 tile (up_dot2_kernels.h) with the
+// mixer in its epilogue (UpMixEpilogue, upmix_kernels.h) and its input staging
+// fed from bits instead of a symbol buffer (the tile's SRC policy):
+//   QPSK   a symbol is a pure function of two bytes: the staging reads the
+//          bits themselves, 10 bytes for its 5 samples;
+//   SDPSK  a symbol needs the state, a scan over the whole stream.  The
+//          mapper's own launches (tile parities, their scan, the streaming
+//          kernel; mapper.hip) run first on the same stream and leave the
+//          states packed 2 bits each, n/4 bytes, which the staging reads back
+//          as a pure lookup.  No workgroup waits on another.
+// Samples before the call come from the interpolator's history, which holds
+// symbols either way.
+//
+// Dispatch.  The fused kernel takes what upmix_tile_dot2 takes, with d_bits
+// 16-byte aligned (and, in the bank, row strides that are multiples of 16
+// bytes).  Every other legal shape runs srcdsp_mapper_step into scratch and
+// srcdsp_upmix_step from it inside the call; the bank then loops over its
+// channels.  Either way outputs and all three handles' state are those of the
+// three calls, bit for bit.
+#include <algorithm>
+
+#include "mapper_state.h"
+#include "upmix_kernels.h"
+
+namespace srcdsp {
+namespace {
+PathCounter g_fused_calls, g_chain_calls, g_bank_calls, g_loop_calls;
+
+// the tile's input words from bits
+struct UpBitsIn {
+    int kind;
+    const uint8_t *bits;  // QPSK: the row's bits, 16-byte aligned
+    const uint32_t *pk;   // SDPSK: the row's states, 16 per word
+    __device__ __forceinline__ uint32_t at(long j) const {
+        if (kind == MAPPER_QPSK) return mapper_qpsk_word(mapper_qpsk_state(bits[2 * j], bits[2 * j + 1]));
+        return mapper_sdpsk_word((pk[j >> 4] >> (2 * (j & 15))) & 3u);
+    }
+    __device__ __forceinline__ void load5(long s0, uint32_t (&w)[5]) const {
+        if (kind == MAPPER_QPSK) {
+            const uint2 v = *(const uint2 *)(bits + 2 * s0);  // s0 is a multiple of 4
+            const uint32_t e = *(const uint16_t *)(bits + 2 * s0 + 8);
+            const uint32_t m = mapper_nz4(v.x) | (mapper_nz4(v.y) << 4) | (mapper_nz4(e) << 8);
+#pragma unroll
+            for (int k = 0; k < 5; ++k)
+                w[k] = mapper_qpsk_word(mapper_qpsk_state((m >> (2 * k)) & 1u, (m >> (2 * k + 1)) & 1u));
+        } else {
+            const uint32_t x = pk[s0 >> 4] >> (2 * (s0 & 15));  // 4 states: s0 & 15 is 0, 4, 8 or 12
+#pragma unroll
+            for (int k = 0; k < 4; ++k) w[k] = mapper_sdpsk_word((x >> (2 * k)) & 3u);
+            w[4] = at(s0 + 4);
+        }
+    }
+};
+
+struct ModLaunch {
+    UpmixLaunch up;        // in / in_stride unused: the input is bits
+    int kind;
+    const uint8_t *bits;
+    long bits_stride;      // bytes between rows (0: shared)
+    long n_bits;
+    const uint32_t *pk;
+    long pk_stride;        // words between rows
+    uint32_t *st_out[kMaxBatch];  // QPSK: the mapper's end state (null: no bits, no change)
+};
+
+template <int LR, int PPC>
+__global__ __launch_bounds__(kUpBlockD) void modulate_tile_dot2(const ModLaunch Q) {
+    extern __shared__ uint4 ug[];
+    const UpmixLaunch &P = Q.up;
+    const int c = blockIdx.y;
+    int16_t *tab = (int16_t *)((char *)ug + P.tab_off);
+    // visible to the epilogue through the tile's own barriers
+    const unsigned nv = P.N / 8;
+    for (unsigned i = threadIdx.x; i < nv; i += kUpBlockD) ((uint4 *)tab)[i] = ((const uint4 *)P.table)[i];
+    for (unsigned i = 8 * nv + threadIdx.x; i < P.N; i += kUpBlockD) tab[i] = P.table[i];
+    const uint32_t mw = P.mix[c];
+    UpMixEpilogue epi;
+    epi.tab = tab;
+    epi.N = P.N;
+    epi.freq = mw >> 16;
+    epi.phi_tile = phase_at((unsigned long)LR * kUpRD * kUpBlockD * blockIdx.x, mw & 0xffffu, epi.freq, P.N);
+    const uint8_t *row = Q.bits + c * Q.bits_stride;
+    if (Q.kind == MAPPER_QPSK && blockIdx.x == 0 && threadIdx.x == 0 && Q.st_out[c])
+        *Q.st_out[c] = mapper_qpsk_state(row[Q.n_bits - 2], row[Q.n_bits - 1]);  // modulators.h:177, the last pair
+    const UpBitsIn src{Q.kind, row, Q.pk + c * Q.pk_stride};
+    up_dot2_tile<LR, true, 3, PPC>(src, P.n_in, P.n_total, P.hist_in[c], P.hist_out[c], P.pairs, P.H, P.shift,
+                                   P.out + c * P.out_stride, epi);
+}
+
+bool fused_takes(const srcdsp_up_state &u, const MixerState &m, const void *d_bits, const void *d_out) {
+    return upmix_fused_takes(u, m, d_bits, d_out);
+}
+
+// words of a row of packed SDPSK states, rounded to whole 16-byte granules
+size_t pk_row_words(size_t n_bits) { return ((n_bits + kMapperLaneBits - 1) / kMapperLaneBits + 3) & ~(size_t)3; }
+
+// nc <= kMaxBatch chains in one launch of the tile (SDPSK: after the mapper's
+// launches); the shape is one fused_takes accepts
+int fused_launch(const srcdsp_mapper_t *maps, const srcdsp_up_t *ups, const srcdsp_mixer_t *mixers, int nc,
+                 const void *d_bits, size_t bits_stride, void *d_out, size_t out_stride, size_t n_bits, size_t n_sym,
+                 long n_total, bool iter, hipStream_t s) {
+    srcdsp_up_state &u0 = ups[0]->u;
+    MapperState &lead = maps[0]->m;
+    ModLaunch Q{};
+    UpmixLaunch &P = Q.up;
+    Q.kind = lead.kind;
+    Q.bits = (const uint8_t *)d_bits;
+    Q.bits_stride = (long)bits_stride;
+    Q.n_bits = (long)n_bits;
+    if (Q.kind == MAPPER_SDPSK && n_bits) {
+        const size_t rw = pk_row_words(n_bits);
+        int rc = lead.sym.reserve(4 * rw * (size_t)nc);
+        if (!rc) rc = mapper_launch(lead, maps, nc, d_bits, bits_stride, lead.sym.d, rw, n_bits, kMapperStates, s);
+        if (rc) return rc;
+        Q.pk = lead.sym.dev<uint32_t>();
+        Q.pk_stride = (long)rw;
+    }
+    P.out = (uint32_t *)d_out;
+    P.pairs = u0.d_pair;
+    P.table = mixers[0]->m.d_table;
+    P.n_in = (long)n_sym;
+    P.n_total = n_total;
+    P.out_stride = (long)out_stride;
+    P.H = u0.H;
+    P.shift = iter ? 0u : (unsigned)(15 - u0.left_shift_factor);
+    P.N = mixers[0]->m.N;
+    const size_t tile_lds = up_dot2_smem(u0.H, u0.L);
+    P.tab_off = (unsigned)tile_lds;
+    const size_t smem = tile_lds + ((2 * (size_t)P.N + 15) & ~(size_t)15);
+    const bool qpsk_state = Q.kind == MAPPER_QPSK && n_bits;
+    for (int c = 0; c < nc; ++c) {
+        MixerState &m = mixers[c]->m;
+        int rc = chan_begin(ups[c]->u, s, P.hist_in[c], P.hist_out[c]);
+        if (!rc) rc = m.order.before(s);
+        if (!rc && qpsk_state) {
+            MapperRowState row;
+            rc = mapper_begin(maps[c]->m, s, row);
+            Q.st_out[c] = row.out;
+        }
+        if (rc) return rc;
+        P.mix[c] = m.word();
+    }
+    constexpr int TI = kUpRD * kUpBlockD;
+    const int PP = (u0.H + 1) / 2;
+    const dim3 grid((unsigned)((n_total + TI - 1) / TI), (unsigned)nc);
+#define SRCDSP_MOD(LR, PPV) hipLaunchKernelGGL((modulate_tile_dot2<LR, PPV>), grid, dim3(kUpBlockD), smem, s, Q)
+    // the compile-time shapes of up_tile_dot2: 16, 32 or 64 taps per phase
+#define SRCDSP_MOD_PP(LR, PPV)        \
+    if (u0.L == LR && PP == PPV) {    \
+        SRCDSP_MOD(LR, PPV);          \
+    } else
+    SRCDSP_MOD_PP(2, 8)
+    SRCDSP_MOD_PP(2, 16)
+    SRCDSP_MOD_PP(2, 32)
+    SRCDSP_MOD_PP(4, 8)
+    SRCDSP_MOD_PP(4, 16)
+    SRCDSP_MOD_PP(4, 32)
+    SRCDSP_MOD_PP(8, 8)
+    SRCDSP_MOD_PP(8, 16)
+#undef SRCDSP_MOD_PP
+    switch (u0.L) {
+    case 2: SRCDSP_MOD(2, 0); break;
+    case 3: SRCDSP_MOD(3, 0); break;
+    case 4: SRCDSP_MOD(4, 0); break;
+    case 5: SRCDSP_MOD(5, 0); break;
+    case 6: SRCDSP_MOD(6, 0); break;
+    case 7: SRCDSP_MOD(7, 0); break;
+    default: SRCDSP_MOD(8, 0); break;
+    }
+#undef SRCDSP_MOD
+    SRCDSP_HIP_TRY(hipGetLastError());
+    const unsigned long n_out = (unsigned long)u0.L * (unsigned long)n_total;
+    for (int c = 0; c < nc; ++c) {
+        MixerState &m = mixers[c]->m;
+        m.advance(n_out);
+        int rc = chan_commit(ups[c]->u, s);
+        if (!rc) rc = m.order.after(s);
+        // SDPSK: the tile read the mapper's packed states, so the mapper's
+        // next step (which may rewrite them) is ordered after the tile too
+        if (!rc && n_bits) rc = qpsk_state ? mapper_commit(maps[c]->m, s) : maps[c]->m.order.after(s);
+        if (rc) return rc;
+    }
+    return SRCDSP_OK;
+}
+
+// every size and type rule of one chain, before anything changes
+int modulate_check(const MapperState &mp, const srcdsp_up_state &u, size_t n_bits, size_t *n_sym, size_t *n_out,
+                   bool flush, const char *who) {
+    if (u.variant == UV_I16_I32) {
+        set_error(std::string(who) + ": a real int16_t interpolator cannot take complex<int16_t> symbols");
+        return SRCDSP_ERR_UNSUPPORTED;
+    }
+    if (mp.kind == MAPPER_QPSK && n_bits % 2 != 0) {
+        set_error(std::string(who) + ": a QPSK step takes an even number of bits (modulators.h:171)");
+        return SRCDSP_ERR_SIZE;
+    }
+    *n_sym = mapper_n_out(mp.kind, n_bits);
+    *n_out = (size_t)u.L * (*n_sym + (flush ? u.length / u.L : 0));
+    return SRCDSP_OK;
+}
+
+// one checked chain of n_out > 0; *fused tells which path served it
+int modulate_one(srcdsp_mapper_t mapper, srcdsp_up_t up, srcdsp_mixer_t mixer, const void *d_bits, size_t n_bits,
+                 size_t n_sym, void *d_out, size_t n_out, bool flush, bool iter, void *stream, bool *fused) {
+    srcdsp_up_state &u = up->u;
+    if (fused_takes(u, mixer->m, d_bits, d_out)) {
+        *fused = true;
+        return fused_launch(&mapper, &up, &mixer, 1, d_bits, 0, d_out, 0, n_bits, n_sym,
+                            (long)(n_out / u.L), iter, (hipStream_t)stream);
+    }
+    *fused = false;
+    MapperState &mp = mapper->m;
+    int rc = mp.touch();  // the symbols are the mapper's scratch: its event orders their reuse
+    if (!rc) rc = mp.sym.reserve(4 * std::max<size_t>(n_sym, 1));
+    if (!rc && n_bits) rc = srcdsp_mapper_step(mapper, d_bits, n_bits, mp.sym.d, n_sym, stream);
+    if (!rc) rc = srcdsp_upmix_step(up, mixer, mp.sym.d, n_sym, d_out, n_out, flush, iter, stream);
+    if (!rc) rc = mp.order.after((hipStream_t)stream);
+    return rc;
+}
+
+}  // namespace
+}  // namespace srcdsp
+
+using namespace srcdsp;
+
+extern "C" {
+
+SRCDSP_API int srcdsp_modulate_step(srcdsp_mapper_t mapper, srcdsp_up_t up, srcdsp_mixer_t mixer, const void *d_bits,
+                                    size_t n_bits, void *d_out, size_t n_out, int flush, int iterator, void *stream) {
+    SRCDSP_ARG_CHECK(mapper != nullptr && up != nullptr && mixer != nullptr, "modulate_step: null handle");
+    size_t n_sym = 0, want = 0;
+    int rc = modulate_check(mapper->m, up->u, n_bits, &n_sym, &want, flush != 0, "modulate_step");
+    if (rc) return rc;
+    if (n_out != want) {
+        set_error("modulate_step: output must hold exactly L*symbols samples (L*(symbols + length/L) when flushing)");
+        return SRCDSP_ERR_SIZE;
+    }
+    if (n_out == 0) return SRCDSP_OK;
+    SRCDSP_ARG_CHECK(d_out && (d_bits || n_bits == 0), "modulate_step: null buffer");
+    bool fused = false;
+    rc = modulate_one(mapper, up, mixer, d_bits, n_bits, n_sym, d_out, n_out, flush != 0, iterator != 0, stream, &fused);
+    if (rc == SRCDSP_OK) (fused ? g_fused_calls : g_chain_calls).hit();
+    return rc;
+}
+
+SRCDSP_API int srcdsp_modulate_step_batched(const srcdsp_mapper_t *mappers, const srcdsp_up_t *ups,
+                                            const srcdsp_mixer_t *mixers, int channels, const void *d_bits,
+                                            size_t bits_stride, void *d_out, size_t out_stride, size_t n_bits,
+                                            int flush, void *stream) {
+    SRCDSP_ARG_CHECK(mappers != nullptr && ups != nullptr && mixers != nullptr && channels >= 1,
+                     "modulate_step_batched: no handles");
+    int rc = check_handles(mappers, channels, "modulate_step_batched");
+    if (!rc) rc = check_handles(ups, channels, "modulate_step_batched");
+    if (!rc) rc = check_handles(mixers, channels, "modulate_step_batched");
+    if (rc) return rc;
+    const srcdsp_up_state &u0 = ups[0]->u;
+    const MixerState &m0 = mixers[0]->m;
+    size_t n_sym = 0, n_out = 0;
+    rc = modulate_check(mappers[0]->m, u0, n_bits, &n_sym, &n_out, flush != 0, "modulate_step_batched");
+    if (rc) return rc;
+    for (int c = 1; c < channels; ++c) {
+        const srcdsp_up_state &uc = ups[c]->u;
+        SRCDSP_ARG_CHECK(mappers[c]->m.kind == mappers[0]->m.kind, "modulate_step_batched: mappers must share a kind");
+        SRCDSP_ARG_CHECK(uc.variant == u0.variant && uc.L == u0.L && uc.h_raw == u0.h_raw,
+                         "modulate_step_batched: interpolators must share variant, L and taps");
+        SRCDSP_ARG_CHECK(mixers[c]->m.N == m0.N, "modulate_step_batched: mixers must share N");
+    }
+    SRCDSP_ARG_CHECK(bits_stride == 0 || bits_stride >= n_bits,
+                     "modulate_step_batched: bits_stride must be 0 (shared) or >= n_bits");
+    if (out_stride < n_out) {
+        set_error("modulate_step_batched: out_stride must hold a row of L*(symbols + length/L when flushing) samples");
+        return SRCDSP_ERR_SIZE;
+    }
+    if (n_out == 0) return SRCDSP_OK;
+    SRCDSP_ARG_CHECK(d_out && (d_bits || n_bits == 0), "modulate_step_batched: null buffer");
+    if (!(fused_takes(u0, m0, d_bits, d_out) && bits_stride % 16 == 0 && (out_stride * 4) % 16 == 0)) {
+        g_loop_calls.hit();
+        for (int c = 0; c < channels && !rc; ++c) {
+            bool fused;
+            rc = modulate_one(mappers[c], ups[c], mixers[c], chan_row(d_bits, c, bits_stride, 1), n_bits, n_sym,
+                              chan_row(d_out, c, out_stride), n_out, flush != 0, false, stream, &fused);
+        }
+        return rc;
+    }
+    g_bank_calls.hit();
+    for (int c0 = 0; c0 < channels && !rc; c0 += kMaxBatch)
+        rc = fused_launch(mappers + c0, ups + c0, mixers + c0, std::min(kMaxBatch, channels - c0),
+                          chan_row(d_bits, c0, bits_stride, 1), bits_stride, chan_row(d_out, c0, out_stride), out_stride,
+                          n_bits, n_sym, (long)(n_out / u0.L), false, (hipStream_t)stream);
+    return rc;
+}
+
+SRCDSP_API int srcdsp_modulate_stats(unsigned long *fused_calls, unsigned long *chain_calls, unsigned long *bank_calls,
+                                     unsigned long *loop_calls) {
+    g_fused_calls.read(fused_calls);
+    g_chain_calls.read(chain_calls);
+    g_bank_calls.read(bank_calls);
+    g_loop_calls.read(loop_calls);
+    return SRCDSP_OK;
+}
+
+}  // extern "C"

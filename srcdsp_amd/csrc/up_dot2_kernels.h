@@ -65,6 +65,20 @@ inline size_t up_dot2_smem(int H, unsigned L) {
     return 4 * 16 * (size_t)PGR > out_lds ? 4 * 16 * (size_t)PGR : out_lds;
 }
 
+// Where a tile's input words come from (the staging policy SRC of
+// up_dot2_tile): at(j) is input sample j, 0 <= j < n_in, as a packed word;
+// load5 the five samples from s0 (a multiple of 4, all five inside the input).
+// This one reads the words of a sample buffer, as upsamp.hip and upmix.hip do.
+struct UpWordsIn {
+    const uint32_t *in;
+    __device__ __forceinline__ uint32_t at(long j) const { return in[j]; }
+    __device__ __forceinline__ void load5(long s0, uint32_t (&w)[5]) const {
+        const uint4 v = *(const uint4 *)(in + s0);
+        w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+        w[4] = in[s0 + 4];
+    }
+};
+
 // the interpolator alone: every packed output word is stored as it is
 struct UpStoreEpilogue {
     __device__ __forceinline__ void begin(int) {}
@@ -78,11 +92,12 @@ struct UpStoreEpilogue {
 // PPC: pairs per phase as a compile-time constant (0: runtime, from H): the
 // chunk loop unrolls completely, the window sets rotate without register
 // copies and each accumulator starts with a dot2 into an inline 0.
+// SRC: where the input words come from (UpWordsIn: a sample buffer).
 // EPI: what happens to a lane's 8 LR packed output words on their way to the
 // output tile: epi.begin(k) with k the lane's first output word within the
 // tile, then epi(word) once per word in output order.
-template <int LR, bool NTS, int WS, int PPC, class EPI>
-__device__ __forceinline__ void up_dot2_tile(const uint32_t *in, long n_in, long n_total, const uint32_t *hist_in,
+template <int LR, bool NTS, int WS, int PPC, class EPI, class SRC>
+__device__ __forceinline__ void up_dot2_tile(const SRC &src, long n_in, long n_total, const uint32_t *hist_in,
                                              uint32_t *hist_out, const uint32_t *pairs, int H, unsigned shift,
                                              uint32_t *out, EPI &epi) {
     constexpr int R = kUpRD, TI = R * kUpBlockD;
@@ -92,10 +107,15 @@ __device__ __forceinline__ void up_dot2_tile(const uint32_t *in, long n_in, long
     const int HG = (PP + 3) / 4;         // halo granules per plane (window reach: dword D0 - PP)
     const int PGR = TI / 8 + HG;         // granules per plane (4 dwords = 8 samples)
     const int t = threadIdx.x;
+    // sample j of the virtual stream (history ++ input ++ flush zeros)
+    auto fetch = [&](long j) -> uint32_t {
+        if (j < 0) return j + Hm1 < 0 ? 0u : hist_in[j + Hm1];
+        return j >= n_in ? 0u : src.at(j);
+    };
     if (blockIdx.x == 0) {
         for (int k = t; k < Hm1; k += kUpBlockD) {
             const long j = n_total - Hm1 + k;
-            hist_out[k] = up_fetch<UV_CI16_I32>(in, hist_in, j, n_in, Hm1);
+            hist_out[k] = fetch(j);
         }
     }
     const long j0 = (long)blockIdx.x * TI;
@@ -123,10 +143,7 @@ __device__ __forceinline__ void up_dot2_tile(const uint32_t *in, long n_in, long
         for (int i = 0; i < NI; ++i) {
             const int g = t + i * kUpBlockD;
             if (i < 2 || g < ng) {  // ng >= 2 * kUpBlockD
-                const long s0 = j0 - 8L * HG + 4L * g;
-                const uint4 v = *(const uint4 *)(in + s0);
-                w[i][0] = v.x; w[i][1] = v.y; w[i][2] = v.z; w[i][3] = v.w;
-                w[i][4] = in[s0 + 4];
+                src.load5(j0 - 8L * HG + 4L * g, w[i]);
             }
         }
 #pragma unroll
@@ -138,12 +155,10 @@ __device__ __forceinline__ void up_dot2_tile(const uint32_t *in, long n_in, long
         const long s0 = j0 - 8L * HG + 4L * g;
         uint32_t w[5];
         if (s0 >= 0 && s0 + 5 <= n_in) {
-            const uint4 v = *(const uint4 *)(in + s0);
-            w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-            w[4] = in[s0 + 4];
+            src.load5(s0, w);
         } else {
 #pragma unroll
-            for (int k = 0; k < 5; ++k) w[k] = up_fetch<UV_CI16_I32>(in, hist_in, s0 + k, n_in, Hm1);
+            for (int k = 0; k < 5; ++k) w[k] = fetch(s0 + k);
         }
         put(g, w);
     }

@@ -25,43 +25,11 @@
 
 #include "ops.h"
 
-#include "nco_device.h"
-#include "up_dot2_kernels.h"
+#include "upmix_kernels.h"
 
 namespace srcdsp {
 namespace {
 PathCounter g_fused_calls, g_pair_calls, g_bank_calls, g_loop_calls;
-
-constexpr unsigned kUpmixMaxN = 4096;  // table entries staged in LDS (8 KiB)
-
-struct UpmixLaunch {
-    const uint32_t *in;
-    uint32_t *out;
-    const uint32_t *pairs;   // shared by all channels
-    const int16_t *table;    // one table for all: built from N alone (mixers.h:155-158)
-    long n_in, n_total;
-    long in_stride, out_stride;  // samples, between channels (grid.y)
-    int H;
-    unsigned shift, N;
-    unsigned tab_off;        // byte offset of the table in dynamic LDS
-    const uint32_t *hist_in[kMaxBatch];
-    uint32_t *hist_out[kMaxBatch];
-    uint32_t mix[kMaxBatch];  // lo: phase, hi: frequency word
-};
-
-// the mixer on a lane's consecutive output words
-struct UpMixEpilogue {
-    const int16_t *tab;
-    unsigned N, freq, phi_tile;  // phi_tile: phase of the tile's first output
-    unsigned ph;
-    __device__ __forceinline__ void begin(int k) { ph = (phi_tile + ((unsigned)k % N) * freq) % N; }
-    __device__ __forceinline__ uint32_t operator()(uint32_t w) {
-        const uint32_t y = nco_mix(w, tab, N, ph);
-        ph += freq;
-        ph = ph >= N ? ph - N : ph;
-        return y;
-    }
-};
 
 template <int LR, int PPC>
 __global__ __launch_bounds__(kUpBlockD) void upmix_tile_dot2(const UpmixLaunch P) {
@@ -78,16 +46,11 @@ __global__ __launch_bounds__(kUpBlockD) void upmix_tile_dot2(const UpmixLaunch P
     epi.N = P.N;
     epi.freq = mw >> 16;
     epi.phi_tile = phase_at((unsigned long)LR * kUpRD * kUpBlockD * blockIdx.x, mw & 0xffffu, epi.freq, P.N);
-    up_dot2_tile<LR, true, 3, PPC>(P.in + c * P.in_stride, P.n_in, P.n_total, P.hist_in[c], P.hist_out[c], P.pairs,
-                                   P.H, P.shift, P.out + c * P.out_stride, epi);
+    up_dot2_tile<LR, true, 3, PPC>(UpWordsIn{P.in + c * P.in_stride}, P.n_in, P.n_total, P.hist_in[c], P.hist_out[c],
+                                   P.pairs, P.H, P.shift, P.out + c * P.out_stride, epi);
 }
 
-bool fused_takes(const srcdsp_up_state &u, const MixerState &m, const void *d_in, const void *d_out) {
-    return u.variant == UV_CI16_I32 && u.coef_i16 && u.L >= 2 && u.L <= 8 && u.ntaps <= kUpMaxTaps &&
-           m.N <= kUpmixMaxN && aligned16(d_in) && aligned16(d_out);
-}
-
-// nc <= kMaxBatch chains in one launch; the shape is one fused_takes accepts
+// nc <= kMaxBatch chains in one launch; the shape is one upmix_fused_takes accepts
 int fused_launch(const srcdsp_up_t *ups, const srcdsp_mixer_t *mixers, int nc, const void *d_in, size_t in_stride,
                  void *d_out, size_t out_stride, size_t n_in, long n_total, bool iter, hipStream_t s) {
     srcdsp_up_state &u0 = ups[0]->u;
@@ -170,7 +133,7 @@ int upmix_one(srcdsp_up_t up, srcdsp_mixer_t mixer, const void *d_in, size_t n_i
     }
     if (n_out == 0) return SRCDSP_OK;
     SRCDSP_ARG_CHECK(d_out && (d_in || n_in == 0), "upmix_step: null buffer");
-    if (fused_takes(u, mixer->m, d_in, d_out)) {
+    if (upmix_fused_takes(u, mixer->m, d_in, d_out)) {
         *fused = true;
         return fused_launch(&up, &mixer, 1, d_in, 0, d_out, 0, n_in, (long)(n_in + extra), iter, (hipStream_t)stream);
     }
@@ -224,7 +187,7 @@ SRCDSP_API int srcdsp_upmix_step_batched(const srcdsp_up_t *ups, const srcdsp_mi
     }
     if (n_out == 0) return SRCDSP_OK;
     SRCDSP_ARG_CHECK(d_out && (d_in || n_in == 0), "upmix_step_batched: null buffer");
-    if (!(fused_takes(u0, m0, d_in, d_out) && (in_stride * 4) % 16 == 0 && (out_stride * 4) % 16 == 0)) {
+    if (!(upmix_fused_takes(u0, m0, d_in, d_out) && (in_stride * 4) % 16 == 0 && (out_stride * 4) % 16 == 0)) {
         g_loop_calls.hit();
         for (int c = 0; c < channels && !rc; ++c) {
             bool fused;

@@ -189,7 +189,7 @@ __global__ __launch_bounds__(kUpBlockD, MINW) void up_tile_dot2(const uint32_t *
                                                          const uint32_t *hist_in, uint32_t *hist_out,
                                                          const uint32_t *pairs, int H, unsigned shift, uint32_t *out) {
     UpStoreEpilogue epi;
-    up_dot2_tile<LR, NTS, WS, PPC>(in, n_in, n_total, hist_in, hist_out, pairs, H, shift, out, epi);
+    up_dot2_tile<LR, NTS, WS, PPC>(UpWordsIn{in}, n_in, n_total, hist_in, hist_out, pairs, H, shift, out, epi);
 }
 
 static int in_bytes(int v) { return v == UV_I16_I32 ? 2 : 4; }

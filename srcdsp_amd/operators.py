@@ -483,6 +483,140 @@ def upmix_stats():
     return tuple(x.value for x in v)
 
 
+# ================================================================ symbol mappers
+def _bits(x):
+    """Bits as the reference takes them: one uint8_t each, a one when non-zero."""
+    if _is_device(x):
+        import torch
+        if x.dtype != torch.uint8:
+            raise TypeError("device bits must be a uint8 tensor")
+        return x
+    return np.ascontiguousarray(x, np.uint8).reshape(-1)
+
+
+class _SymbolMapper(_Handle):
+    _destroy = "srcdsp_mapper_destroy"
+    _clone = "srcdsp_mapper_clone"
+    _kind_id = 0
+
+    def __init__(self, T="int16_t"):
+        if _kind(T) != "i16":
+            raise TypeError("only the int16_t symbol mappers are provided (amplitude 8192, modulators.h:34-39)")
+        self._h = C.c_void_p()
+        A.call("srcdsp_mapper_create", C.byref(self._h), self._kind_id)
+
+    def reset(self):
+        A.call("srcdsp_mapper_reset", self._h)
+
+    def state(self) -> int:
+        k, s = C.c_int(), C.c_int()
+        A.call("srcdsp_mapper_get_state", self._h, C.byref(k), C.byref(s))
+        return s.value
+
+    def setState(self, state: int):
+        """Not a reference method: set the state (0..3) so a bit stream can be
+        split in time."""
+        A.call("srcdsp_mapper_set_state", self._h, int(state))
+
+    def n_out(self, n_bits: int) -> int:
+        return n_bits // 2 if self._kind_id == 1 else n_bits
+
+    def step(self, bits, out=None):
+        b = _bits(bits)
+        n = b.numel() if _is_device(b) else b.size
+        if out is None:
+            if self._kind_id == 1 and n % 2:
+                raise A.SrcdspError("srcdsp_mapper_step", A.ERR_SIZE, "a QPSK step takes an even number of bits")
+            out = _alloc_like(b, "ci16", self.n_out(n))
+        if _is_device(b):
+            A.call("srcdsp_mapper_step", self._h, _ptr(b), n, _ptr(out), _nsamples(out, "ci16"), _stream(b))
+        else:
+            A.call("srcdsp_mapper_step_host", self._h, _ptr(b), n, _ptr(out), _nsamples(out, "ci16"))
+        return out
+
+
+class SymbolMapperSdpsk(_SymbolMapper):
+    """dsptl::SymbolMapperSdpsk<int16_t> (modulators.h:82-131): one symbol per bit."""
+    _kind_id = 0
+
+
+class SymbolMapperQpsk(_SymbolMapper):
+    """dsptl::SymbolMapperQpsk<int16_t> (modulators.h:147-198): one symbol per bit pair."""
+    _kind_id = 1
+
+
+def _bank_bits(bits, ch, who):
+    if not _is_device(bits) or _bits(bits).dim() not in (1, 2):
+        raise ValueError(f"{who}: bits is a uint8 device tensor [n] (shared) or [C, n]")
+    shared = bits.dim() == 1
+    if not shared and bits.shape[0] != ch:
+        raise ValueError(f"{who}: one row of bits per channel")
+    return shared, bits.shape[-1]
+
+
+def mapper_step_batched(mappers, bits, out):
+    """Step C symbol mappers of one kind in one call: row c is exactly
+    ``mappers[c].step``.  ``bits`` of shape [n] is shared by every row; of
+    shape [C, n] one row each.  ``out`` is int16 [C, >= symbols, 2]; columns
+    past a row's symbols are left untouched.  Device tensors."""
+    ch = len(mappers)
+    if ch < 1:
+        raise ValueError("mapper bank: at least one channel")
+    shared, n = _bank_bits(bits, ch, "mapper bank")
+    if not _is_device(out) or out.dim() != 3 or out.shape[-1] != 2 or out.shape[0] != ch:
+        raise ValueError("mapper bank: out is an int16 device tensor [C, symbols, 2]")
+    A.call("srcdsp_mapper_step_batched", _handles(mappers), ch, _ptr(bits), 0 if shared else n, _ptr(out),
+           out.shape[1], n, _stream(bits))
+    return out
+
+
+class ModulatorChain:
+    """mapper.step(bits, sym); up.step(sym, tmp, flush); mixer.step(tmp, out) in
+    one call (the transmit chain from bits).  All three operators' state
+    advances exactly as the three calls."""
+
+    def __init__(self, mapper: _SymbolMapper, up: FilterUpsamplingFir, mixer: Mixer):
+        self.mapper, self.up, self.mixer = mapper, up, mixer
+
+    def step(self, bits, out=None, flush: bool = False, iterator: bool = False):
+        if not _is_device(bits):
+            return self.mixer.step(self.up.step(self.mapper.step(bits), None, flush, iterator), out)
+        b = _bits(bits)
+        n = b.numel()
+        if out is None:
+            extra = self.up.L * (self.up.getLength() // self.up.L) if flush else 0
+            out = _alloc_like(b, "ci16", self.mapper.n_out(n) * self.up.L + extra)
+        A.call("srcdsp_modulate_step", self.mapper._h, self.up._h, self.mixer._h, _ptr(b), n, _ptr(out),
+               _nsamples(out, "ci16"), int(flush), int(iterator), _stream(b))
+        return out
+
+
+def modulate_step_batched(mappers, ups, mixers, bits, out, flush: bool = False):
+    """Step C mapper -> interpolator -> mixer chains in one call: row c is
+    exactly ``ModulatorChain(mappers[c], ups[c], mixers[c]).step``.  ``bits``
+    [n] is shared, [C, n] one row per channel; ``out`` is int16 [C, >=
+    L*(symbols + length/L when flushing), 2].  Device tensors."""
+    ch = len(mappers)
+    if ch < 1 or len(ups) != ch or len(mixers) != ch:
+        raise ValueError("modulator bank: one mapper, interpolator and mixer per channel, at least one channel")
+    shared, n = _bank_bits(bits, ch, "modulator bank")
+    if not _is_device(out) or out.dim() != 3 or out.shape[-1] != 2 or out.shape[0] != ch:
+        raise ValueError("modulator bank: out is an int16 device tensor [C, samples, 2]")
+    A.call("srcdsp_modulate_step_batched", _handles(mappers), _handles(ups), _handles(mixers), ch, _ptr(bits),
+           0 if shared else n, _ptr(out), out.shape[1], n, int(flush), _stream(bits))
+    return out
+
+
+def modulate_stats():
+    """(fused_calls, chain_calls, bank_calls, loop_calls): single modulator
+    calls served by the fused kernel and by the mapper followed by the
+    interpolator -> mixer call, batched calls served by one launch and by the
+    per-channel loop, process-wide."""
+    v = [C.c_ulong() for _ in range(4)]
+    A.call("srcdsp_modulate_stats", *[C.byref(x) for x in v])
+    return tuple(x.value for x in v)
+
+
 # ======================================================== FixedPatternCorrelator
 class FixedPatternCorrelator(_Handle):
     """dsptl::FixedPatternCorrelator<int16_t, int32_t, N, S> (correlators.h:54-316)."""
