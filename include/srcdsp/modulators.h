@@ -13,6 +13,11 @@
  * srcdsp_mapper_step_batched, and straight onto a carrier through
  * srcdsp_modulate_step(_batched).
  *
+ * dsptl::QStagger is an extension with no reference class: the delay line on
+ * the Q rail that makes the QPSK mapper's signal offset QPSK (the reference
+ * leaves it to the application); srcdsp_modulate_offset_step(_batched) runs it
+ * inside the transmit chain.
+ *
  * Where the reference asserts (bits.size() against out.size(), :106 and :171)
  * the calls fail as the other drop-ins do (assert, or std::runtime_error
  * under NDEBUG).
@@ -69,6 +74,47 @@ class SymbolMapperSdpsk<int16_t> : public srcdsp_detail::MapperBase<SRCDSP_MAPPE
 
 template <>
 class SymbolMapperQpsk<int16_t> : public srcdsp_detail::MapperBase<SRCDSP_MAPPER_QPSK> {};
+
+/// Extension (no reference class): the offset of offset-QPSK, which the
+/// reference leaves to the application ("for QPSK or OQPSK modulations",
+/// modulators.h:147): a delay line of D samples, 1..64, on the imaginary rail
+/// between FilterUpsamplingFir::step and Mixer::step.  out[i] = (re(in[i]),
+/// im(in[i - D])), the first D imaginary halves carried over from the step
+/// before (zeros at first).  A value type like the mappers; in and out may not
+/// overlap.  srcdsp_modulate_offset_step(_batched) takes handle().
+class QStagger {
+public:
+    explicit QStagger(unsigned D) : h_(nullptr) { srcdsp_detail::check(srcdsp_stagger_create(&h_, D), "QStagger"); }
+    ~QStagger() { srcdsp_stagger_destroy(h_); }
+    QStagger(const QStagger &o) : h_(srcdsp_detail::clone_handle(o.h_, srcdsp_stagger_clone, "QStagger(copy)")) {}
+    QStagger(QStagger &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    QStagger &operator=(QStagger o) noexcept {
+        std::swap(h_, o.h_);
+        return *this;
+    }
+
+    void step(const std::vector<std::complex<int16_t>> &in, std::vector<std::complex<int16_t>> &out) {
+        srcdsp_detail::check_shape(in.size() == out.size(), "QStagger::step: in and out differ in size");
+        srcdsp_detail::check(srcdsp_stagger_step_host(h_, in.data(), in.size(), out.data()), "step");
+    }
+    /// device samples in, device samples out
+    void step(const DeviceSpan<const std::complex<int16_t>> &in, DeviceSpan<std::complex<int16_t>> out,
+              void *stream = nullptr) {
+        srcdsp_detail::check_shape(in.size == out.size, "QStagger::step: in and out differ in size");
+        srcdsp_detail::check(srcdsp_stagger_step(h_, in.data, in.size, out.data, stream), "step(device)");
+    }
+    /// the carry back to zeros
+    void reset() { srcdsp_detail::check(srcdsp_stagger_reset(h_), "reset"); }
+    unsigned getDelay() const {
+        unsigned d = 0;
+        srcdsp_detail::check(srcdsp_stagger_get_state(h_, &d, nullptr), "getDelay");
+        return d;
+    }
+    srcdsp_stagger_t handle() const { return h_; }
+
+private:
+    srcdsp_stagger_t h_;
+};
 
 }  // namespace dsptl
 #endif

@@ -329,6 +329,81 @@ SRCDSP_API int srcdsp_modulate_stats(unsigned long *fused_calls, unsigned long *
                                      unsigned long *bank_calls, unsigned long *loop_calls);
 
 /* ============================================================================
+ * The OQPSK Q-rail stagger: an extension with no reference class.
+ * SymbolMapperQpsk is "for QPSK or OQPSK modulations" (modulators.h:147-198);
+ * the offset is the application's there: a delay line of half a symbol (L/2
+ * output samples) on the imaginary rail between FilterUpsamplingFir::step
+ * (upsampling_filters.h:149-233) and Mixer::step (mixers.h:169-188).  This is
+ * that delay line.  With v = carry ++ im(in[0..n)):
+ *   out[i] = (re(in[i]), v[i])     i.e. im(in[i-D]), or carry[i] for i < D
+ *   carry' = v[n .. n+D)           the last D imaginary halves, also for n < D
+ * ==========================================================================*/
+typedef struct srcdsp_stagger *srcdsp_stagger_t;
+/* Extension (between upsampling_filters.h:149-233 and mixers.h:169-188): a
+ * delay of D samples, 1 <= D <= 64 (SRCDSP_ERR_ARG otherwise), carry 0.  No
+ * device call: a handle is a host object until it steps on device buffers. */
+SRCDSP_API int srcdsp_stagger_create(srcdsp_stagger_t *out, unsigned D);
+SRCDSP_API int srcdsp_stagger_destroy(srcdsp_stagger_t h);
+/* Extension: a value copy, D and the carry (waits for the last step) */
+SRCDSP_API int srcdsp_stagger_clone(srcdsp_stagger_t h, srcdsp_stagger_t *out);
+/* Extension: carry = 0, as a new handle */
+SRCDSP_API int srcdsp_stagger_reset(srcdsp_stagger_t h);
+/* Extension: D and the carry (D int16_t, carry[i] is the imaginary half of the
+ * next step's out[i]); waits for the handle's last step.  Null pointers are
+ * skipped. */
+SRCDSP_API int srcdsp_stagger_get_state(srcdsp_stagger_t h, unsigned *D, int16_t *carry);
+/* Extension: the samples one workgroup of the kernel covers, the largest D */
+SRCDSP_API int srcdsp_stagger_geometry(int *tile_samples, unsigned *max_delay);
+/* Extension (the delay between up.step, upsampling_filters.h:149-233, and
+ * mixer.step, mixers.h:169-188): one step on device buffers of n
+ * complex<int16_t> each.  d_in and d_out may not overlap (SRCDSP_ERR_ARG): a
+ * sample is read again D samples later.  n == 0 changes nothing.  A refused
+ * call changes no handle. */
+SRCDSP_API int srcdsp_stagger_step(srcdsp_stagger_t h, const void *d_in, size_t n, void *d_out, void *stream);
+SRCDSP_API int srcdsp_stagger_step_host(srcdsp_stagger_t h, const void *in, size_t n, void *out);
+/* Extension.  C staggers in one call: row c reads d_in + c*in_stride samples
+ * and writes d_out + c*out_stride samples exactly as srcdsp_stagger_step(hs[c],
+ * ...) would.  in_stride == 0: every row reads the SAME samples; otherwise
+ * in_stride >= n.  out_stride >= n (SRCDSP_ERR_SIZE otherwise).  The staggers
+ * share D (their carries may differ), every handle is listed once, channels >=
+ * 1, and the two arrays do not overlap (SRCDSP_ERR_ARG otherwise). */
+SRCDSP_API int srcdsp_stagger_step_batched(const srcdsp_stagger_t *hs, int channels, const void *d_in,
+                                           size_t in_stride, void *d_out, size_t out_stride, size_t n, void *stream);
+
+/* Extension.  Mapper -> FilterUpsamplingFir -> stagger -> Mixer, the offset-QPSK
+ * transmit chain from bits: mapper.step(bits, sym) (modulators.h:103-117 /
+ * :169-184); up.step(sym, tmp, flush) (upsampling_filters.h:149-233;
+ * iterator=1: :240-323); srcdsp_stagger_step(tmp, tmp2); mixer.step(tmp2, out)
+ * (mixers.h:169-188) in one call.  Sizes and refusals as srcdsp_modulate_step;
+ * any mapper kind.  All four handles end as the four calls leave them, bit for
+ * bit: the carry holds the last D imaginary outputs after the interpolator's
+ * clamp and before the mixer.
+ * One kernel (srcdsp_modulate_step's, the delay between the interpolator's
+ * clamp and the mixer epilogue) serves what that call's kernel serves with
+ * D <= L; every other shape runs the four operators inside the call. */
+SRCDSP_API int srcdsp_modulate_offset_step(srcdsp_mapper_t mapper, srcdsp_up_t up, srcdsp_stagger_t stagger,
+                                           srcdsp_mixer_t mixer, const void *d_bits, size_t n_bits, void *d_out,
+                                           size_t n_out, int flush, int iterator, void *stream);
+/* Extension.  C such chains in one call: row c is
+ * srcdsp_modulate_offset_step(mappers[c], ups[c], staggers[c], mixers[c], ...)
+ * (modulators.h:103-117 / :169-184, upsampling_filters.h:149-233,
+ * mixers.h:169-188), rows and strides as srcdsp_modulate_step_batched.  The
+ * staggers share D as the mappers share a kind; every handle is listed once
+ * (SRCDSP_ERR_ARG otherwise).  One launch (grid.y = channel) serves the single
+ * call's kernel shapes when the row strides are multiples of 16 bytes; every
+ * other shape loops over the channels. */
+SRCDSP_API int srcdsp_modulate_offset_step_batched(const srcdsp_mapper_t *mappers, const srcdsp_up_t *ups,
+                                                   const srcdsp_stagger_t *staggers, const srcdsp_mixer_t *mixers,
+                                                   int channels, const void *d_bits, size_t bits_stride, void *d_out,
+                                                   size_t out_stride, size_t n_bits, int flush, void *stream);
+/* Extension.  Process-wide counters (the paths of modulators.h:103-184 ->
+ * upsampling_filters.h:149-233 -> stagger -> mixers.h:169-188): single calls
+ * served by the fused kernel / by the four operators, batched calls served by
+ * one launch / by the per-channel loop */
+SRCDSP_API int srcdsp_modulate_offset_stats(unsigned long *fused_calls, unsigned long *chain_calls,
+                                            unsigned long *bank_calls, unsigned long *loop_calls);
+
+/* ============================================================================
  * FixedPatternCorrelator<int16_t, int32_t, N, S>   (correlators.h:54-316)
  * ==========================================================================*/
 typedef struct srcdsp_corr *srcdsp_corr_t;

@@ -79,6 +79,18 @@ SIGNATURES = {
     "srcdsp_modulate_step": (I, [VP, VP, VP, VP, SZ, VP, SZ, I, I, VP]),
     "srcdsp_modulate_step_batched": (I, [HP, HP, HP, I, VP, SZ, VP, SZ, SZ, I, VP]),
     "srcdsp_modulate_stats": (I, [C.POINTER(C.c_ulong)] * 4),
+    "srcdsp_stagger_create": (I, [HP, U]),
+    "srcdsp_stagger_destroy": (I, [VP]),
+    "srcdsp_stagger_clone": (I, [VP, HP]),
+    "srcdsp_stagger_reset": (I, [VP]),
+    "srcdsp_stagger_get_state": (I, [VP, UP, I16P]),
+    "srcdsp_stagger_geometry": (I, [IP, UP]),
+    "srcdsp_stagger_step": (I, [VP, VP, SZ, VP, VP]),
+    "srcdsp_stagger_step_host": (I, [VP, VP, SZ, VP]),
+    "srcdsp_stagger_step_batched": (I, [HP, I, VP, SZ, VP, SZ, SZ, VP]),
+    "srcdsp_modulate_offset_step": (I, [VP, VP, VP, VP, VP, SZ, VP, SZ, I, I, VP]),
+    "srcdsp_modulate_offset_step_batched": (I, [HP, HP, HP, HP, I, VP, SZ, VP, SZ, SZ, I, VP]),
+    "srcdsp_modulate_offset_stats": (I, [C.POINTER(C.c_ulong)] * 4),
     "srcdsp_corr_create": (I, [HP, U, U]),
     "srcdsp_corr_destroy": (I, [VP]),
     "srcdsp_corr_clone": (I, [VP, HP]),

@@ -1,0 +1,308 @@
+// modulate_offset.hip -- SymbolMapper{Sdpsk,Qpsk} -> FilterUpsamplingFir ->
+// Q-rail stagger -> Mixer in one call: the offset-QPSK transmit chain from
+// bits (modulators.h:103-117 / :169-184, upsampling_filters.h:149-233, a delay
+// of D samples on the imaginary rail, mixers.h:169-188), single
+// (srcdsp_modulate_offset_step) and as a bank (srcdsp_modulate_offset_step_batched).
+//
+// The kernel is modulate.hip's tile with the tile's stagger policy switched on
+// (up_dot2_kernels.h, STG): the delay acts on the clamped interpolator output,
+// ahead of the mixer epilogue.  Of the two ways to give a later tile's first
+// lane the D values before the tile, this one recomputes them from the halo
+// the tile has staged anyway (D lanes, ceil(H/2) dot2 each), so the call stays
+// one launch and no workgroup waits on another; a launch of its own that
+// writes them per tile would read every tile's halo from memory a second
+// time.  The Q rail has no tap table of its own.
+//
+// Dispatch.  The fused kernel takes what modulate_tile_dot2 takes with
+// 1 <= D <= L.  Every other legal shape runs the four operators inside the
+// call through grow-only scratch: srcdsp_mapper_step, srcdsp_up_step,
+// srcdsp_stagger_step into d_out, srcdsp_mixer_step in place; the bank then
+// loops over its channels.  Either way outputs and all four handles' state
+// are those of the four calls, bit for bit.
+#include <algorithm>
+
+#include "modulate_kernels.h"
+#include "stagger_state.h"
+
+namespace srcdsp {
+namespace {
+PathCounter g_fused_calls, g_chain_calls, g_bank_calls, g_loop_calls;
+
+// the tile's stagger policy (STG of up_dot2_tile)
+struct UpQStagger {
+    static constexpr bool on = true;
+    int D;                    // 1..LR
+    const int16_t *carry_in;  // D values: the imaginary halves of the call's first D outputs
+    int16_t *carry_out;
+    uint16_t *slot;           // 8 values in LDS: the halves ahead of the tile's first word, the last D used
+
+    // lanes t < D, while the planes still hold the tile's input: value t of the
+    // D ahead of the tile, and of the D that end the call (its last tile only).
+    // tile_q(jr, o): clamped imaginary output of phase o of staged sample jr;
+    // halo: the staged index of the tile's first sample
+    template <int LR, class F>
+    __device__ __forceinline__ void seed(int t, long j0, long n_total, int halo, F &tile_q) const {
+        if (t >= D) return;
+        const int o = LR - D + t;
+        slot[8 - D + t] = j0 == 0 ? (uint16_t)carry_in[t] : (uint16_t)tile_q(halo - 1, o);
+        const long jl = n_total - 1 - j0;
+        if (jl < kUpRD * kUpBlockD) carry_out[t] = (int16_t)(uint16_t)tile_q(halo + (int)jl, o);
+    }
+    __device__ __forceinline__ uint4 seeds() const { return *(const uint4 *)slot; }
+};
+
+struct ModOffLaunch {
+    ModLaunch mod;
+    int D;
+    unsigned slot_off;  // byte offset of the seed slot in dynamic LDS
+    const int16_t *carry_in[kMaxBatch];
+    int16_t *carry_out[kMaxBatch];
+};
+
+template <int LR, int PPC>
+__global__ __launch_bounds__(kUpBlockD) void modoffset_tile_dot2(const ModOffLaunch A) {
+    extern __shared__ uint4 ug[];
+    const ModLaunch &Q = A.mod;
+    const UpmixLaunch &P = Q.up;
+    const int c = blockIdx.y;
+    int16_t *tab = (int16_t *)((char *)ug + P.tab_off);
+    // visible to the epilogue through the tile's own barriers
+    const unsigned nv = P.N / 8;
+    for (unsigned i = threadIdx.x; i < nv; i += kUpBlockD) ((uint4 *)tab)[i] = ((const uint4 *)P.table)[i];
+    for (unsigned i = 8 * nv + threadIdx.x; i < P.N; i += kUpBlockD) tab[i] = P.table[i];
+    const uint32_t mw = P.mix[c];
+    UpMixEpilogue epi;
+    epi.tab = tab;
+    epi.N = P.N;
+    epi.freq = mw >> 16;
+    epi.phi_tile = phase_at((unsigned long)LR * kUpRD * kUpBlockD * blockIdx.x, mw & 0xffffu, epi.freq, P.N);
+    const uint8_t *row = Q.bits + c * Q.bits_stride;
+    if (Q.kind == MAPPER_QPSK && blockIdx.x == 0 && threadIdx.x == 0 && Q.st_out[c])
+        *Q.st_out[c] = mapper_qpsk_state(row[Q.n_bits - 2], row[Q.n_bits - 1]);  // modulators.h:177, the last pair
+    const UpBitsIn src{Q.kind, row, Q.pk + c * Q.pk_stride};
+    const UpQStagger stg{A.D, A.carry_in[c], A.carry_out[c], (uint16_t *)((char *)ug + A.slot_off)};
+    up_dot2_tile<LR, true, 3, PPC>(src, P.n_in, P.n_total, P.hist_in[c], P.hist_out[c], P.pairs, P.H, P.shift,
+                                   P.out + c * P.out_stride, epi, stg);
+}
+
+bool fused_takes(const srcdsp_up_state &u, const MixerState &m, const StaggerState &g, const void *d_bits,
+                 const void *d_out) {
+    return upmix_fused_takes(u, m, d_bits, d_out) && g.D <= u.L;
+}
+
+// nc <= kMaxBatch chains in one launch of the tile (SDPSK: after the mapper's
+// launches); the shape is one fused_takes accepts
+int fused_launch(const srcdsp_mapper_t *maps, const srcdsp_up_t *ups, const srcdsp_stagger_t *stags,
+                 const srcdsp_mixer_t *mixers, int nc, const void *d_bits, size_t bits_stride, void *d_out,
+                 size_t out_stride, size_t n_bits, size_t n_sym, long n_total, bool iter, hipStream_t s) {
+    srcdsp_up_state &u0 = ups[0]->u;
+    MapperState &lead = maps[0]->m;
+    ModOffLaunch A{};
+    ModLaunch &Q = A.mod;
+    UpmixLaunch &P = Q.up;
+    A.D = (int)stags[0]->g.D;
+    Q.kind = lead.kind;
+    Q.bits = (const uint8_t *)d_bits;
+    Q.bits_stride = (long)bits_stride;
+    Q.n_bits = (long)n_bits;
+    if (Q.kind == MAPPER_SDPSK && n_bits) {
+        const size_t rw = pk_row_words(n_bits);
+        int rc = lead.sym.reserve(4 * rw * (size_t)nc);
+        if (!rc) rc = mapper_launch(lead, maps, nc, d_bits, bits_stride, lead.sym.d, rw, n_bits, kMapperStates, s);
+        if (rc) return rc;
+        Q.pk = lead.sym.dev<uint32_t>();
+        Q.pk_stride = (long)rw;
+    }
+    P.out = (uint32_t *)d_out;
+    P.pairs = u0.d_pair;
+    P.table = mixers[0]->m.d_table;
+    P.n_in = (long)n_sym;
+    P.n_total = n_total;
+    P.out_stride = (long)out_stride;
+    P.H = u0.H;
+    P.shift = iter ? 0u : (unsigned)(15 - u0.left_shift_factor);
+    P.N = mixers[0]->m.N;
+    const size_t tile_lds = up_dot2_smem(u0.H, u0.L);
+    P.tab_off = (unsigned)tile_lds;
+    A.slot_off = (unsigned)(tile_lds + ((2 * (size_t)P.N + 15) & ~(size_t)15));
+    const size_t smem = A.slot_off + 16;
+    const bool qpsk_state = Q.kind == MAPPER_QPSK && n_bits;
+    for (int c = 0; c < nc; ++c) {
+        MixerState &m = mixers[c]->m;
+        int rc = chan_begin(ups[c]->u, s, P.hist_in[c], P.hist_out[c]);
+        if (!rc) rc = m.order.before(s);
+        if (!rc) rc = stagger_begin(stags[c]->g, s, A.carry_in[c], A.carry_out[c]);
+        if (!rc && qpsk_state) {
+            MapperRowState row;
+            rc = mapper_begin(maps[c]->m, s, row);
+            Q.st_out[c] = row.out;
+        }
+        if (rc) return rc;
+        P.mix[c] = m.word();
+    }
+    constexpr int TI = kUpRD * kUpBlockD;
+    const int PP = (u0.H + 1) / 2;
+    const dim3 grid((unsigned)((n_total + TI - 1) / TI), (unsigned)nc);
+#define SRCDSP_MODOFF(LR, PPV) hipLaunchKernelGGL((modoffset_tile_dot2<LR, PPV>), grid, dim3(kUpBlockD), smem, s, A)
+    // the compile-time shapes of up_tile_dot2: 16, 32 or 64 taps per phase
+#define SRCDSP_MODOFF_PP(LR, PPV)     \
+    if (u0.L == LR && PP == PPV) {    \
+        SRCDSP_MODOFF(LR, PPV);       \
+    } else
+    SRCDSP_MODOFF_PP(2, 8)
+    SRCDSP_MODOFF_PP(2, 16)
+    SRCDSP_MODOFF_PP(2, 32)
+    SRCDSP_MODOFF_PP(4, 8)
+    SRCDSP_MODOFF_PP(4, 16)
+    SRCDSP_MODOFF_PP(4, 32)
+    SRCDSP_MODOFF_PP(8, 8)
+    SRCDSP_MODOFF_PP(8, 16)
+#undef SRCDSP_MODOFF_PP
+    switch (u0.L) {
+    case 2: SRCDSP_MODOFF(2, 0); break;
+    case 3: SRCDSP_MODOFF(3, 0); break;
+    case 4: SRCDSP_MODOFF(4, 0); break;
+    case 5: SRCDSP_MODOFF(5, 0); break;
+    case 6: SRCDSP_MODOFF(6, 0); break;
+    case 7: SRCDSP_MODOFF(7, 0); break;
+    default: SRCDSP_MODOFF(8, 0); break;
+    }
+#undef SRCDSP_MODOFF
+    SRCDSP_HIP_TRY(hipGetLastError());
+    const unsigned long n_out = (unsigned long)u0.L * (unsigned long)n_total;
+    for (int c = 0; c < nc; ++c) {
+        MixerState &m = mixers[c]->m;
+        m.advance(n_out);
+        int rc = chan_commit(ups[c]->u, s);
+        if (!rc) rc = m.order.after(s);
+        if (!rc) rc = stagger_commit(stags[c]->g, s);
+        // SDPSK: the tile read the mapper's packed states, so the mapper's
+        // next step (which may rewrite them) is ordered after the tile too
+        if (!rc && n_bits) rc = qpsk_state ? mapper_commit(maps[c]->m, s) : maps[c]->m.order.after(s);
+        if (rc) return rc;
+    }
+    return SRCDSP_OK;
+}
+
+// one checked chain of n_out > 0; *fused tells which path served it
+int modoff_one(srcdsp_mapper_t mapper, srcdsp_up_t up, srcdsp_stagger_t stag, srcdsp_mixer_t mixer,
+               const void *d_bits, size_t n_bits, size_t n_sym, void *d_out, size_t n_out, bool flush, bool iter,
+               void *stream, bool *fused) {
+    srcdsp_up_state &u = up->u;
+    if (fused_takes(u, mixer->m, stag->g, d_bits, d_out)) {
+        *fused = true;
+        return fused_launch(&mapper, &up, &stag, &mixer, 1, d_bits, 0, d_out, 0, n_bits, n_sym, (long)(n_out / u.L),
+                            iter, (hipStream_t)stream);
+    }
+    *fused = false;
+    MapperState &mp = mapper->m;
+    StaggerState &g = stag->g;
+    // the symbols are the mapper's scratch, the interpolator's output the
+    // stagger's: their events order the reuse
+    int rc = mp.touch();
+    if (!rc) rc = g.touch();
+    if (!rc) rc = mp.order.before((hipStream_t)stream);
+    if (!rc) rc = g.order.before((hipStream_t)stream);
+    if (!rc) rc = mp.sym.reserve(4 * std::max<size_t>(n_sym, 1));
+    if (!rc) rc = g.scratch.reserve(4 * n_out);
+    if (!rc && n_bits) rc = srcdsp_mapper_step(mapper, d_bits, n_bits, mp.sym.d, n_sym, stream);
+    if (!rc) rc = srcdsp_up_step(up, mp.sym.d, n_sym, g.scratch.d, n_out, flush, iter, stream);
+    if (!rc) rc = srcdsp_stagger_step(stag, g.scratch.d, n_out, d_out, stream);
+    if (!rc) rc = srcdsp_mixer_step(mixer, d_out, n_out, d_out, stream);
+    if (!rc) rc = mp.order.after((hipStream_t)stream);
+    if (!rc) rc = g.order.after((hipStream_t)stream);
+    return rc;
+}
+
+}  // namespace
+}  // namespace srcdsp
+
+using namespace srcdsp;
+
+extern "C" {
+
+SRCDSP_API int srcdsp_modulate_offset_step(srcdsp_mapper_t mapper, srcdsp_up_t up, srcdsp_stagger_t stagger,
+                                           srcdsp_mixer_t mixer, const void *d_bits, size_t n_bits, void *d_out,
+                                           size_t n_out, int flush, int iterator, void *stream) {
+    SRCDSP_ARG_CHECK(mapper != nullptr && up != nullptr && stagger != nullptr && mixer != nullptr,
+                     "modulate_offset_step: null handle");
+    size_t n_sym = 0, want = 0;
+    int rc = modulate_check(mapper->m, up->u, n_bits, &n_sym, &want, flush != 0, "modulate_offset_step");
+    if (rc) return rc;
+    if (n_out != want) {
+        set_error("modulate_offset_step: output must hold exactly L*symbols samples (L*(symbols + length/L) when "
+                  "flushing)");
+        return SRCDSP_ERR_SIZE;
+    }
+    if (n_out == 0) return SRCDSP_OK;
+    SRCDSP_ARG_CHECK(d_out && (d_bits || n_bits == 0), "modulate_offset_step: null buffer");
+    bool fused = false;
+    rc = modoff_one(mapper, up, stagger, mixer, d_bits, n_bits, n_sym, d_out, n_out, flush != 0, iterator != 0, stream,
+                    &fused);
+    if (rc == SRCDSP_OK) (fused ? g_fused_calls : g_chain_calls).hit();
+    return rc;
+}
+
+SRCDSP_API int srcdsp_modulate_offset_step_batched(const srcdsp_mapper_t *mappers, const srcdsp_up_t *ups,
+                                                   const srcdsp_stagger_t *staggers, const srcdsp_mixer_t *mixers,
+                                                   int channels, const void *d_bits, size_t bits_stride, void *d_out,
+                                                   size_t out_stride, size_t n_bits, int flush, void *stream) {
+    const char *who = "modulate_offset_step_batched";
+    SRCDSP_ARG_CHECK(mappers != nullptr && ups != nullptr && staggers != nullptr && mixers != nullptr && channels >= 1,
+                     "modulate_offset_step_batched: no handles");
+    int rc = check_handles(mappers, channels, who);
+    if (!rc) rc = check_handles(ups, channels, who);
+    if (!rc) rc = check_handles(staggers, channels, who);
+    if (!rc) rc = check_handles(mixers, channels, who);
+    if (rc) return rc;
+    const srcdsp_up_state &u0 = ups[0]->u;
+    const MixerState &m0 = mixers[0]->m;
+    size_t n_sym = 0, n_out = 0;
+    rc = modulate_check(mappers[0]->m, u0, n_bits, &n_sym, &n_out, flush != 0, who);
+    if (rc) return rc;
+    for (int c = 1; c < channels; ++c) {
+        const srcdsp_up_state &uc = ups[c]->u;
+        SRCDSP_ARG_CHECK(mappers[c]->m.kind == mappers[0]->m.kind,
+                         "modulate_offset_step_batched: mappers must share a kind");
+        SRCDSP_ARG_CHECK(uc.variant == u0.variant && uc.L == u0.L && uc.h_raw == u0.h_raw,
+                         "modulate_offset_step_batched: interpolators must share variant, L and taps");
+        SRCDSP_ARG_CHECK(staggers[c]->g.D == staggers[0]->g.D,
+                         "modulate_offset_step_batched: staggers must share D");
+        SRCDSP_ARG_CHECK(mixers[c]->m.N == m0.N, "modulate_offset_step_batched: mixers must share N");
+    }
+    SRCDSP_ARG_CHECK(bits_stride == 0 || bits_stride >= n_bits,
+                     "modulate_offset_step_batched: bits_stride must be 0 (shared) or >= n_bits");
+    if (out_stride < n_out) {
+        set_error("modulate_offset_step_batched: out_stride must hold a row of L*(symbols + length/L when flushing) "
+                  "samples");
+        return SRCDSP_ERR_SIZE;
+    }
+    if (n_out == 0) return SRCDSP_OK;
+    SRCDSP_ARG_CHECK(d_out && (d_bits || n_bits == 0), "modulate_offset_step_batched: null buffer");
+    if (!(fused_takes(u0, m0, staggers[0]->g, d_bits, d_out) && bits_stride % 16 == 0 && (out_stride * 4) % 16 == 0)) {
+        g_loop_calls.hit();
+        for (int c = 0; c < channels && !rc; ++c) {
+            bool fused;
+            rc = modoff_one(mappers[c], ups[c], staggers[c], mixers[c], chan_row(d_bits, c, bits_stride, 1), n_bits,
+                            n_sym, chan_row(d_out, c, out_stride), n_out, flush != 0, false, stream, &fused);
+        }
+        return rc;
+    }
+    g_bank_calls.hit();
+    for (int c0 = 0; c0 < channels && !rc; c0 += kMaxBatch)
+        rc = fused_launch(mappers + c0, ups + c0, staggers + c0, mixers + c0, std::min(kMaxBatch, channels - c0),
+                          chan_row(d_bits, c0, bits_stride, 1), bits_stride, chan_row(d_out, c0, out_stride),
+                          out_stride, n_bits, n_sym, (long)(n_out / u0.L), false, (hipStream_t)stream);
+    return rc;
+}
+
+SRCDSP_API int srcdsp_modulate_offset_stats(unsigned long *fused_calls, unsigned long *chain_calls,
+                                            unsigned long *bank_calls, unsigned long *loop_calls) {
+    g_fused_calls.read(fused_calls);
+    g_chain_calls.read(chain_calls);
+    g_bank_calls.read(bank_calls);
+    g_loop_calls.read(loop_calls);
+    return SRCDSP_OK;
+}
+
+}  // extern "C"

@@ -1,7 +1,8 @@
 // up_dot2_kernels.h -- the interpolator's handle layout and its v_dot2 tile
 // (FilterUpsamplingFir, upsampling_filters.h:36-326), shared by upsamp.hip
 // (srcdsp_up_step) and upmix.hip (the interpolator -> mixer chain, which runs
-// the same tile with the mixer in its output epilogue).
+// the same tile with the mixer in its output epilogue); modulate.hip feeds it
+// from bits and modulate_offset.hip adds the OQPSK stagger ahead of the mixer.
 #pragma once
 #include <string>
 
@@ -85,6 +86,22 @@ struct UpStoreEpilogue {
     __device__ __forceinline__ uint32_t operator()(uint32_t w) { return w; }
 };
 
+// no stagger between the clamp and the epilogue: the tile as upsamp.hip,
+// upmix.hip and modulate.hip run it
+struct UpNoStagger {
+    static constexpr bool on = false;
+};
+
+// the uniform delay d (1..K) as a compile-time constant: f(integral_constant<int, d>)
+template <int K, class F>
+__device__ __forceinline__ void up_stagger_dispatch(int d, F &f) {
+    if (d == K) {
+        f(std::integral_constant<int, K>{});
+    } else if constexpr (K > 1) {
+        up_stagger_dispatch<K - 1>(d, f);
+    }
+}
+
 // One tile (blockIdx.x) of the call.
 // WS: window register sets (3: the next granule is read a chunk ahead, 150
 // VGPRs at LR = 4; 2: it is read at the end of the chunk into the set that
@@ -96,10 +113,19 @@ struct UpStoreEpilogue {
 // EPI: what happens to a lane's 8 LR packed output words on their way to the
 // output tile: epi.begin(k) with k the lane's first output word within the
 // tile, then epi(word) once per word in output order.
-template <int LR, bool NTS, int WS, int PPC, class EPI, class SRC>
+// STG: a delay of stg.D <= LR output words on the imaginary rail between the
+// clamp and the epilogue (UpNoStagger: none; the OQPSK stagger of
+// modulate_offset.hip).  Output word idx of a lane takes its imaginary half
+// from word idx - D: of the lane itself, or of the lane before through the
+// padding granule of its output chunk (after the second barrier, so across
+// waves too).  The tile's first lane takes them from stg.seed: the carry
+// (tile 0) or the last phases of the sample before the tile, recomputed from
+// the halo the planes hold (D lanes, ceil(H/2) dot2 each; no workgroup waits
+// on another).  The same D lanes of the call's last tile write the new carry.
+template <int LR, bool NTS, int WS, int PPC, class EPI, class SRC, class STG = UpNoStagger>
 __device__ __forceinline__ void up_dot2_tile(const SRC &src, long n_in, long n_total, const uint32_t *hist_in,
                                              uint32_t *hist_out, const uint32_t *pairs, int H, unsigned shift,
-                                             uint32_t *out, EPI &epi) {
+                                             uint32_t *out, EPI &epi, const STG &stg = STG()) {
     constexpr int R = kUpRD, TI = R * kUpBlockD;
     extern __shared__ uint4 ug[];  // 4 planes (E_re, E_im, O_re, O_im) of PGR granules each
     const int Hm1 = H - 1;
@@ -163,6 +189,24 @@ __device__ __forceinline__ void up_dot2_tile(const SRC &src, long n_in, long n_t
         put(g, w);
     }
     __syncthreads();
+    if constexpr (STG::on) {
+        // (ahead of the main loop, where no accumulator is live: behind it the
+        // unrolled loop was scheduled for 180 instead of 77 VGPRs at (2, 32))
+        // the clamped imaginary output of phase o of staged sample jr (counted
+        // from the planes' first sample), on one lane: the pairs of the main
+        // loop, p-th pair on dword m - p of plane E_im (jr = 2m + 1) or dword
+        // m - 1 - p of plane O_im (jr = 2m)
+        auto tile_q = [&](int jr, int o) -> uint32_t {
+            const uint32_t *pq = pl + ((jr & 1) ? 1 * PDW + (jr >> 1) : 3 * PDW + (jr >> 1) - 1);
+            int32_t acc = 0;
+#pragma unroll 8  // 8 tap and 8 plane loads in flight
+            for (int p = 0; p < PP; ++p)
+                acc = __builtin_amdgcn_sdot2(__builtin_bit_cast(short2_t_u, pq[-p]),
+                                             __builtin_bit_cast(short2_t_u, pairs[p * LR + o]), acc, false);
+            return limit_t16_pair(0, acc, shift) >> 16;
+        };
+        stg.template seed<LR>(t, j0, n_total, 8 * HG, tile_q);
+    }
     // lane base: input j0 + 8t = plane dword D0 = 4t + 4*HG (granule gb).  Input
     // r, pair p reads dword D0 + k - p, k = r/2 - 1 in plane O for even r,
     // k = (r-1)/2 in plane E for odd r:
@@ -281,16 +325,43 @@ __device__ __forceinline__ void up_dot2_tile(const SRC &src, long n_in, long n_t
     // profiles/tuning/r03_up_stage_ab.txt)
     __syncthreads();                    // every wave is done reading the planes
     uint4 *ob = ug;
-    epi.begin(R * LR * t);
+    auto word = [&](int idx) { return limit_t16_pair(yr[idx % LR][idx / LR], yi[idx % LR][idx / LR], shift); };
+    uint32_t qp[4] = {0, 0, 0, 0};     // the 8 imaginary halves before the lane's first word, two per dword
+    if constexpr (STG::on) {
+        constexpr int T0 = R * LR - 8;
+        ob[t * STR + GPLo] = make_uint4(hi(word(T0), word(T0 + 1)), hi(word(T0 + 2), word(T0 + 3)),
+                                        hi(word(T0 + 4), word(T0 + 5)), hi(word(T0 + 6), word(T0 + 7)));
+        __syncthreads();
+        const uint4 v = t ? ob[(t - 1) * STR + GPLo] : stg.seeds();
+        qp[0] = v.x; qp[1] = v.y; qp[2] = v.z; qp[3] = v.w;
+    }
+    auto emit = [&](auto dc) {
+        constexpr int DC = decltype(dc)::value;  // 0: no stagger
+        epi.begin(R * LR * t);
 #pragma unroll
-    for (int k = 0; k < GPLo; ++k) {
-        uint32_t w4[4];
+        for (int k = 0; k < GPLo; ++k) {
+            uint32_t w4[4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int idx = 4 * k + u, r = idx / LR, o = idx % LR;
-            w4[u] = epi(limit_t16_pair(yr[o][r], yi[o][r], shift));
+            for (int u = 0; u < 4; ++u) {
+                const int idx = 4 * k + u;
+                uint32_t w = word(idx);
+                if constexpr (DC > 0) {
+                    if (idx >= DC) {
+                        w = __builtin_amdgcn_perm(word(idx - DC), w, 0x07060100u);
+                    } else {
+                        const int e = 8 + idx - DC;
+                        w = __builtin_amdgcn_perm(qp[e >> 1], w, (e & 1) ? 0x07060100u : 0x05040100u);
+                    }
+                }
+                w4[u] = epi(w);
+            }
+            ob[t * STR + k] = make_uint4(w4[0], w4[1], w4[2], w4[3]);
         }
-        ob[t * STR + k] = make_uint4(w4[0], w4[1], w4[2], w4[3]);
+    };
+    if constexpr (STG::on) {
+        up_stagger_dispatch<LR>(stg.D, emit);
+    } else {
+        emit(std::integral_constant<int, 0>{});
     }
     __syncthreads();
     const long wbase = (long)LR * j0;             // first output word of the tile

@@ -617,6 +617,127 @@ def modulate_stats():
     return tuple(x.value for x in v)
 
 
+# =========================================================== OQPSK Q-rail stagger
+class QStagger(_Handle):
+    """The offset of offset-QPSK (no reference class): a delay line of D
+    samples, 1..64, on the imaginary rail of complex<int16_t> samples, between
+    the interpolator and the mixer.  ``out[i] = (re(in[i]), im(in[i - D]))``,
+    the first D imaginary halves coming from the carry of the step before."""
+
+    _destroy = "srcdsp_stagger_destroy"
+    _clone = "srcdsp_stagger_clone"
+
+    def __init__(self, D: int):
+        self._h = C.c_void_p()
+        A.call("srcdsp_stagger_create", C.byref(self._h), int(D))
+        self.D = int(D)
+
+    def reset(self):
+        A.call("srcdsp_stagger_reset", self._h)
+
+    def state(self) -> np.ndarray:
+        """The carry: the imaginary halves of the next step's first D outputs."""
+        d = C.c_uint()
+        carry = np.zeros(self.D, np.int16)
+        A.call("srcdsp_stagger_get_state", self._h, C.byref(d), carry.ctypes.data_as(A.I16P))
+        return carry
+
+    def step(self, inp, out=None):
+        n = _nsamples(inp, "ci16")
+        if out is None:
+            out = _alloc_like(inp, "ci16", n)
+        if _is_device(inp):
+            A.call("srcdsp_stagger_step", self._h, _ptr(inp), n, _ptr(out), _stream(inp))
+        else:
+            x = _host(inp, "ci16")
+            A.call("srcdsp_stagger_step_host", self._h, _ptr(x), n, _ptr(out))
+        return out
+
+
+def stagger_geometry():
+    """(tile_samples, max_delay) of the stagger's kernel."""
+    t, d = C.c_int(), C.c_uint()
+    A.call("srcdsp_stagger_geometry", C.byref(t), C.byref(d))
+    return t.value, d.value
+
+
+def stagger_step_batched(staggers, inp, out):
+    """Step C staggers of one D in one call: row c is exactly
+    ``staggers[c].step``.  ``inp`` int16 [n, 2] is shared by every row, [C, n,
+    2] one row each; ``out`` is int16 [C, >= n, 2], columns past n untouched.
+    Device tensors."""
+    ch = len(staggers)
+    if ch < 1:
+        raise ValueError("stagger bank: at least one channel")
+    if not (_is_device(inp) and _is_device(out)):
+        raise ValueError("stagger bank: device tensors only")
+    if inp.dim() not in (2, 3) or inp.shape[-1] != 2 or out.dim() != 3 or out.shape[-1] != 2:
+        raise ValueError("stagger bank: inp is int16 [n, 2] (shared) or [C, n, 2], out int16 [C, n, 2]")
+    shared = inp.dim() == 2
+    if (not shared and inp.shape[0] != ch) or out.shape[0] != ch:
+        raise ValueError("stagger bank: one input row (or one shared input) and one output row per channel")
+    n = inp.shape[-2]
+    A.call("srcdsp_stagger_step_batched", _handles(staggers), ch, _ptr(inp), 0 if shared else n, _ptr(out),
+           out.shape[1], n, _stream(inp))
+    return out
+
+
+class OffsetModulatorChain:
+    """mapper.step(bits, sym); up.step(sym, tmp, flush); stagger.step(tmp, tmp2);
+    mixer.step(tmp2, out) in one call (the offset-QPSK transmit chain from
+    bits).  All four operators' state advances exactly as the four calls."""
+
+    def __init__(self, mapper: _SymbolMapper, up: FilterUpsamplingFir, stagger: QStagger, mixer: Mixer):
+        self.mapper, self.up, self.stagger, self.mixer = mapper, up, stagger, mixer
+
+    def step(self, bits, out=None, flush: bool = False, iterator: bool = False):
+        if not _is_device(bits):
+            y = self.up.step(self.mapper.step(bits), None, flush, iterator)
+            return self.mixer.step(self.stagger.step(y), out)
+        b = _bits(bits)
+        n = b.numel()
+        if out is None:
+            extra = self.up.L * (self.up.getLength() // self.up.L) if flush else 0
+            out = _alloc_like(b, "ci16", self.mapper.n_out(n) * self.up.L + extra)
+        A.call("srcdsp_modulate_offset_step", self.mapper._h, self.up._h, self.stagger._h, self.mixer._h, _ptr(b), n,
+               _ptr(out), _nsamples(out, "ci16"), int(flush), int(iterator), _stream(b))
+        return out
+
+
+def modulate_offset_step(mapper, up, stagger, mixer, bits, out=None, flush: bool = False, iterator: bool = False):
+    """``OffsetModulatorChain(mapper, up, stagger, mixer).step(bits, out, flush, iterator)``."""
+    return OffsetModulatorChain(mapper, up, stagger, mixer).step(bits, out, flush, iterator)
+
+
+def modulate_offset_step_batched(mappers, ups, staggers, mixers, bits, out, flush: bool = False):
+    """Step C mapper -> interpolator -> stagger -> mixer chains in one call:
+    row c is exactly ``OffsetModulatorChain(mappers[c], ups[c], staggers[c],
+    mixers[c]).step``.  ``bits`` [n] is shared, [C, n] one row per channel;
+    ``out`` is int16 [C, >= L*(symbols + length/L when flushing), 2].  Device
+    tensors."""
+    ch = len(mappers)
+    if ch < 1 or len(ups) != ch or len(staggers) != ch or len(mixers) != ch:
+        raise ValueError("offset modulator bank: one mapper, interpolator, stagger and mixer per channel, at least "
+                         "one channel")
+    shared, n = _bank_bits(bits, ch, "offset modulator bank")
+    if not _is_device(out) or out.dim() != 3 or out.shape[-1] != 2 or out.shape[0] != ch:
+        raise ValueError("offset modulator bank: out is an int16 device tensor [C, samples, 2]")
+    A.call("srcdsp_modulate_offset_step_batched", _handles(mappers), _handles(ups), _handles(staggers),
+           _handles(mixers), ch, _ptr(bits), 0 if shared else n, _ptr(out), out.shape[1], n, int(flush),
+           _stream(bits))
+    return out
+
+
+def modulate_offset_stats():
+    """(fused_calls, chain_calls, bank_calls, loop_calls): single offset
+    modulator calls served by the fused kernel and by the four operators,
+    batched calls served by one launch and by the per-channel loop,
+    process-wide."""
+    v = [C.c_ulong() for _ in range(4)]
+    A.call("srcdsp_modulate_offset_stats", *[C.byref(x) for x in v])
+    return tuple(x.value for x in v)
+
+
 # ======================================================== FixedPatternCorrelator
 class FixedPatternCorrelator(_Handle):
     """dsptl::FixedPatternCorrelator<int16_t, int32_t, N, S> (correlators.h:54-316)."""
