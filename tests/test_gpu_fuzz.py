@@ -4,9 +4,23 @@ random chains of step() calls of ragged lengths (including 0 and 1), resets,
 left shifts and coefficient changes, device-resident and host-staged calls
 interleaved.  Every output byte must match.  Shapes are drawn to hit the tuned
 kernels (63/64/127/128/255/256 taps at M = 1/2/3/4/8/16, M = 1, L = 2/4 with 16/32/64
-taps per phase) as often as the generic ones."""
+taps per phase) as often as the generic ones.
+
+The transmit operators (srcdsp_upmix_*, srcdsp_mapper_*, srcdsp_stagger_*,
+srcdsp_modulate_*, srcdsp_modulate_offset_*) are fuzzed as chains against
+tests/tx_chain_model.py, the composition of the mapper model, the oracle's
+interpolator and mixer and the stagger model that tests/test_tx_chain_model.py
+holds to the reference's goldens: ragged steps, flushes in mid-stream, the
+iterator form, retunes, resets, copies, the fused call and the separate
+operators taking turns on the same handles, inputs off 16-byte alignment, and
+banks of 1 to 65 rows at any strides; after every call every output byte and
+every state, the guard band behind every row, and the path counter the
+documented dispatch rule predicts.  The draws are tests/tx_fuzz_draw.py's."""
 import numpy as np
 import pytest
+
+import tx_fuzz_draw as F
+from tx_chain_model import UPMIX, TxChain
 
 pytestmark = pytest.mark.gpu
 
@@ -318,3 +332,102 @@ def test_fuzz_chain_any_shape(S, O, seed):
         exp = od.step(om.step(x))
         assert got.tobytes() == exp.tobytes(), (seed, op, N, Md, nt, n)
         assert m.state()[:2] == om.state()[:2]
+
+
+# --- the transmit chains: every fused family, single calls and banks ---
+
+def _tx_pair(S, O, sh, freq=None, state=None):
+    from tx_gpu import GpuChain
+    freq = sh["freq"] if freq is None else freq
+    state = sh["mapper_state"] if state is None else state
+    args = (sh["family"], sh["L"], sh["taps"], sh["N"], freq)
+    kw = dict(kind=sh["kind"], D=sh["D"], variant=sh["variant"], mapper_state=state)
+    return GpuChain(S, *args, **kw), TxChain(O["strict"], *args, **kw)
+
+
+def _one_hot(i):
+    return tuple(int(k == i) for k in range(4))
+
+
+@pytest.mark.parametrize("seed", range(F.CHAIN_SEEDS))
+def test_fuzz_transmit_chain(S, O, seed):
+    from tx_gpu import GUARD_VALUE, dev, dev_off
+    rng = F.chain_rng(seed)
+    sh = F.draw_shape(rng)
+    ops = F.draw_ops(rng, sh)
+    g, m = _tx_pair(S, O, sh)
+    what = (seed, sh["family"], sh["kind"], sh["L"], sh["H"], sh["variant"], sh["taps_kind"], sh["N"], sh["D"])
+    for k, op in enumerate(ops):
+        if op[0] == "copy":  # go on with copies of all handles
+            g, m = g.copy(), m.copy()
+            continue
+        if op[0] != "step":
+            getattr(g, op[0])(*op[1:])
+            getattr(m, op[0])(*op[1:])
+            continue
+        a = op[1]
+        x = F.draw_input(rng, sh, a["n"])
+        xd = dev_off(x) if a["off"] else dev(x)
+        exp = m.step(x, a["flush"], a["iterator"])
+        s0 = g.stats()
+        if a["fused"]:
+            buf = g.guarded(len(exp))
+            g.fused(xd, a["flush"], a["iterator"], buf[:len(exp)])
+            got = buf.cpu().numpy()
+            assert (got[len(exp):] == GUARD_VALUE).all(), (what, k, a)
+            got = got[:len(exp)]
+        else:
+            got = g.separate(xd, a["flush"], a["iterator"]).cpu().numpy()
+        rose = tuple(b - c for c, b in zip(s0, g.stats()))
+        if not a["fused"] or len(exp) == 0:
+            assert rose == (0, 0, 0, 0), (what, k, a, rose)
+        else:  # the fused kernel where the dispatch rule says so, else the pair / sequence
+            assert rose == _one_hot(0 if F.eligible(sh) and not a["off"] else 1), (what, k, a, rose)
+        assert got.shape == exp.shape and got.tobytes() == exp.tobytes(), (what, k, a)
+        assert g.state() == m.state(), (what, k, a)
+
+
+@pytest.mark.parametrize("seed", range(F.BANK_SEEDS))
+def test_fuzz_transmit_bank(S, O, seed):
+    import torch
+    from tx_gpu import GUARD, GUARD_VALUE, bank_step, dev
+    rng = F.bank_rng(seed)
+    sh = F.draw_bank(rng)
+    rows, samples = sh["rows"], sh["family"] == UPMIX
+    what = (seed, sh["family"], sh["kind"], sh["L"], sh["H"], sh["variant"], sh["taps_kind"], sh["N"], sh["D"], rows,
+            sh["shared"])
+    ps = []
+    for r in range(rows):  # every row its own carrier, mapper state, history and carry
+        g, m = _tx_pair(S, O, sh, float(rng.uniform(-1, 1)), int(rng.integers(0, 4)))
+        x = F.draw_input(rng, sh, int(rng.integers(1, 12)))
+        assert g.separate(dev(x)).cpu().numpy().tobytes() == m.step(x).tobytes(), (what, r)
+        ps.append((g, m))
+    chains = [g for g, _ in ps]
+    unit = 4 if samples else 16  # elements in 16 bytes
+    for k, (n_sym, flush) in enumerate(sh["calls"]):
+        xs = [F.draw_input(rng, sh, n_sym) for _ in range(1 if sh["shared"] else rows)]
+        n = len(xs[0])
+        if sh["shared"]:
+            in_stride, xd = 0, dev(xs[0])
+        else:
+            in_stride = (n + unit - 1) // unit * unit + (0 if sh["in_stride16"] else 1)
+            host = np.zeros((rows, in_stride) + xs[0].shape[1:], xs[0].dtype)
+            host[:, :n] = np.stack(xs)
+            xd = dev(host)
+        exps = [m.step(xs[0 if sh["shared"] else r], flush) for r, (_, m) in enumerate(ps)]
+        n_out = len(exps[0])
+        out_stride = (n_out + GUARD + 3) // 4 * 4 + (0 if sh["out_stride16"] else 1)
+        out = torch.full((rows, out_stride, 2), GUARD_VALUE, dtype=torch.int16, device="cuda")
+        s0 = chains[0].stats()
+        bank_step(chains, xd if n else None, in_stride, out, n, flush)
+        rose = tuple(b - c for c, b in zip(s0, chains[0].stats()))
+        strides16 = in_stride * (4 if samples else 1) % 16 == 0 and out_stride * 4 % 16 == 0
+        if n_out == 0:
+            assert rose == (0, 0, 0, 0), (what, k, rose)
+        else:  # one launch per 64 rows where the dispatch rule says so, else the loop over the rows
+            assert rose == _one_hot(2 if F.eligible(sh) and strides16 else 3), (what, k, rose)
+        got = out.cpu().numpy()
+        assert (got[:, n_out:] == GUARD_VALUE).all(), (what, k)
+        for r, (g, m) in enumerate(ps):
+            assert got[r, :n_out].tobytes() == exps[r].tobytes(), (what, k, r)
+            assert g.state() == m.state(), (what, k, r)

@@ -114,7 +114,8 @@ def test_chain_goldens(S, chain):
 
 # -------------------------- fused = the sequence = the model and oracle composition
 N_SYM = (1, 7, 511, 512, 513, 2047, 2048, 2049, 4101)
-# (4, 16): 2 pairs per phase, run-time; (4, 128), (8, 64): compiled in; (3, 15), (2, 32): run-time L / compiled pairs
+# (4, 16), (8, 64): H = 4 / 8 taps per phase, 2 / 4 pairs, the run-time kernels of L = 4 and 8; (4, 128), (2, 32):
+# 16 / 8 pairs compiled in; (3, 15): run-time L
 SHAPES = [(4, 16, 2), (4, 128, 2), (8, 64, 4), (8, 64, 1), (8, 64, 8), (3, 15, 1), (2, 32, 1)]
 WARM = 100
 
