@@ -122,6 +122,20 @@ public:
         if (found) corrIndex = idx;
         return found != 0;
     }
+    /// Extension, no reference counterpart: every detection the loop of step()
+    /// on the remainders makes in `in`, at most maxHits of them, in one call
+    /// (srcdsp_corr_step_all).  corrIndices[k] is relative to `in`;
+    /// bitSamples[k] is what getRefBitSamples() returns after detection k.
+    /// Returns the samples processed: less than in.size() only when maxHits
+    /// was reached, and stepAll on the rest continues.
+    size_t stepAll(const std::vector<std::complex<InType>> &in, int maxHits, std::vector<int> &corrIndices,
+                   std::vector<std::vector<std::complex<InType>>> &bitSamples) {
+        return step_all(in.data(), in.size(), maxHits, corrIndices, bitSamples, nullptr, true);
+    }
+    size_t stepAll(const DeviceSpan<const std::complex<InType>> &in, int maxHits, std::vector<int> &corrIndices,
+                   std::vector<std::vector<std::complex<InType>>> &bitSamples, void *stream = nullptr) {
+        return step_all(in.data, in.size, maxHits, corrIndices, bitSamples, stream, false);
+    }
     /// correlators.h:167-194
     void setPattern(const std::array<std::complex<CompType>, N> &in, double thresholdCoeff = 0.8) {
         std::vector<int32_t> p(2 * N);
@@ -153,6 +167,25 @@ public:
 
 private:
     srcdsp_corr_t h_;
+    size_t step_all(const void *in, size_t n, int maxHits, std::vector<int> &corrIndices,
+                    std::vector<std::vector<std::complex<InType>>> &bitSamples, void *stream, bool host) {
+        // detections lie at least two samples apart: more rows than n / 2 + 1 are never filled
+        if (maxHits > 0 && (size_t)maxHits > n / 2 + 1) maxHits = (int)(n / 2 + 1);
+        const size_t cap = maxHits > 0 ? (size_t)maxHits : 1;
+        std::vector<int> idx(cap);
+        std::vector<std::complex<InType>> rows(cap * N);
+        int hits = 0;
+        size_t consumed = 0;
+        int16_t *bp = reinterpret_cast<int16_t *>(rows.data());
+        srcdsp_detail::check(host ? srcdsp_corr_step_all_host(h_, in, n, maxHits, &hits, idx.data(), bp, &consumed)
+                                  : srcdsp_corr_step_all(h_, in, n, maxHits, &hits, idx.data(), bp, &consumed, stream),
+                             "stepAll");
+        corrIndices.assign(idx.begin(), idx.begin() + hits);
+        bitSamples.clear();
+        for (int k = 0; k < hits; ++k)
+            bitSamples.emplace_back(rows.begin() + (size_t)k * N, rows.begin() + (size_t)(k + 1) * N);
+        return consumed;
+    }
 #ifdef CREATE_DEBUG_FILES
     // correlators.h:108-110 and :254-256: one line per processed sample
     std::ofstream fenergy;

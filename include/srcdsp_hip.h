@@ -452,6 +452,52 @@ SRCDSP_API int srcdsp_corr_step_batched(const srcdsp_corr_t *hs, int channels, c
                                         size_t n, int *found, int *corr_index, void *stream);
 /* process-wide counters: calls served by the bank kernel, calls served by the per-channel loop */
 SRCDSP_API int srcdsp_corr_batched_stats(unsigned long *bank_calls, unsigned long *loop_calls);
+/* Extension (no reference call).  Every detection of a stream in one call:
+ * per channel exactly the application's loop of step() on the remainders
+ * (correlators.h:209-303 called again after each `break`, :291),
+ *
+ *     off = 0; k = 0
+ *     while off < n and k < max_hits:
+ *         found, ci = h.step(in[off:n])
+ *         if not found: off = n; break
+ *         corr_index[k] = off + ci; bits[k] = h.getRefBitSamples()   (:311-316)
+ *         k += 1; off += ci + 2
+ *     n_hits = k; consumed = off
+ *
+ * and nothing else.  corr_index is relative to this call's input; it can be
+ * off - 1, and -1 when the peak was the previous call's last sample.  step
+ * breaks before `top` advances (:291-296), so the detected sample is
+ * overwritten by the next one: the loop scans the stream with every detected
+ * sample removed, and so does this call.  bits_host, [max_hits][N]
+ * complex<int16_t>, receives the bitSamples of each detection and may be NULL.
+ * The handle is left exactly as the loop leaves it: registers, history,
+ * bitSamples of the last detection, stream ordering.  consumed < n only when
+ * max_hits was reached; calling again on d_in + consumed continues the loop.
+ * Synchronous, with at most two host synchronisations per call whatever
+ * `channels` and the number of detections are (the loop path below makes those
+ * of its srcdsp_corr_step calls).  Scratch, owned by hs[0], grows with
+ * channels * min(max_hits, n / 2 + 1) * N samples.
+ * The batched form follows srcdsp_corr_step_batched: handles sharing N and S,
+ * listed once each, any number of them; in_stride == 0 is one shared input;
+ * n_hits[C], consumed[C], corr_index[C][max_hits] and bits_host[C][max_hits][N]
+ * are host arrays.  n == 0 is OK with every n_hits[c] = 0; n > INT_MAX is
+ * SRCDSP_ERR_SIZE; max_hits < 1, channels < 1 or a null result array is
+ * SRCDSP_ERR_ARG.  A refused call changes no handle.
+ * Kernels serve S == 1 with int16-range patterns and N <= 8192 (the shapes of
+ * the fused scan): a candidate pass over the undisturbed stream and a resolve
+ * pass that recomputes the stretch after each accepted detection on the stream
+ * with the detected samples removed.  Every other shape runs the loop above
+ * with srcdsp_corr_step inside the call. */
+SRCDSP_API int srcdsp_corr_step_all(srcdsp_corr_t h, const void *d_in, size_t n, int max_hits, int *n_hits,
+                                    int *corr_index, int16_t *bits_host, size_t *consumed, void *stream);
+/* the same on a host buffer, staged through the handle's pinned buffer */
+SRCDSP_API int srcdsp_corr_step_all_host(srcdsp_corr_t h, const void *in, size_t n, int max_hits, int *n_hits,
+                                         int *corr_index, int16_t *bits_host, size_t *consumed);
+SRCDSP_API int srcdsp_corr_step_all_batched(const srcdsp_corr_t *hs, int channels, const void *d_in, size_t in_stride,
+                                            size_t n, int max_hits, int *n_hits, int *corr_index, int16_t *bits_host,
+                                            size_t *consumed, void *stream);
+/* process-wide counters: calls served by the kernels, calls served by the loop of srcdsp_corr_step */
+SRCDSP_API int srcdsp_corr_all_stats(unsigned long *kernel_calls, unsigned long *loop_calls);
 /* step() as built with CREATE_DEBUG_FILES (correlators.h:107-132, 253-257):
  * also returns, for every sample the call processed, the registers the
  * reference writes to its debug files -- corr_out[k] = corrValue[0] and

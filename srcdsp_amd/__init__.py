@@ -20,7 +20,9 @@ from .operators import (  # noqa: F401
     FixedPatternCorrelator,
     Mixer,
     MixerDecimatorChain,
+    corr_all_stats,
     corr_batched_stats,
+    corr_step_all_batched,
     corr_step_batched,
     decim_step_batched,
     fill_synthetic,
@@ -51,6 +53,6 @@ __all__ = ["FifoWithTimeTrack", "files", "FilterDnsamplingFir", "FilterFir", "Fi
            "QStagger", "stagger_geometry", "stagger_step_batched", "OffsetModulatorChain", "modulate_offset_step",
            "modulate_offset_step_batched", "modulate_offset_stats",
            "FixedPatternCorrelator", "decim_step_batched", "mixdecim_step_batched", "mixdecim_batched_stats",
-           "corr_step_batched", "corr_batched_stats", "DemodulatorOqpsk", "demod_step_batched", "demod_tables",
+           "corr_step_batched", "corr_batched_stats", "corr_step_all_batched", "corr_all_stats", "DemodulatorOqpsk", "demod_step_batched", "demod_tables",
            "FreqEstimator", "estimate_freq", "demod_acquire_batched",
            "fill_synthetic", "SrcdspError", "lib"]

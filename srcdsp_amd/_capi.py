@@ -100,6 +100,10 @@ SIGNATURES = {
     "srcdsp_corr_prime": (I, [VP, VP, SZ, VP]),
     "srcdsp_corr_step_batched": (I, [HP, I, VP, SZ, SZ, IP, IP, VP]),
     "srcdsp_corr_batched_stats": (I, [C.POINTER(C.c_ulong), C.POINTER(C.c_ulong)]),
+    "srcdsp_corr_step_all": (I, [VP, VP, SZ, I, IP, IP, I16P, C.POINTER(C.c_size_t), VP]),
+    "srcdsp_corr_step_all_host": (I, [VP, VP, SZ, I, IP, IP, I16P, C.POINTER(C.c_size_t)]),
+    "srcdsp_corr_step_all_batched": (I, [HP, I, VP, SZ, SZ, I, IP, IP, I16P, C.POINTER(C.c_size_t), VP]),
+    "srcdsp_corr_all_stats": (I, [C.POINTER(C.c_ulong), C.POINTER(C.c_ulong)]),
     "srcdsp_corr_step_host": (I, [VP, VP, SZ, IP, IP]),
     "srcdsp_corr_step_trace": (I, [VP, VP, SZ, IP, IP, U32P, U32P, C.POINTER(C.c_size_t), VP]),
     "srcdsp_corr_step_host_trace": (I, [VP, VP, SZ, IP, IP, U32P, U32P, C.POINTER(C.c_size_t)]),

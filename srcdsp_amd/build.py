@@ -140,14 +140,14 @@ CORR_HIT_PROBE = os.path.join(TEST_BUILD, "libcorr_hit_probe.so")
 # translation units recompiled under a test define.  Never loaded by the package.
 #   corr_exact: the correlator's detection test always on the correctly rounded
 #     square roots (corr_hit.h), in the single-channel scan (corr.hip) and the
-#     batched one (corr_bank.hip), so the suite can require identical
+#     batched ones (corr_bank.hip, corr_all.hip), so the suite can require identical
 #     detections with and without the fast sign test;
 #   shared_dev: multi.hip honouring SRCDSP_COMM_SHARED_DEVICES=1, so the
 #     multi-device C ABI can be rehearsed at ndev > 1 on one GPU through the
 #     test-only communicator library (tests/rccl_stub); named libsrcdsp_hip.so in
 #     its own directory so the C++ test program links it as -lsrcdsp_hip.
 TEST_VARIANTS = {
-    "corr_exact": (("corr.hip", "corr_bank.hip"), "SRCDSP_CORR_ALWAYS_EXACT",
+    "corr_exact": (("corr.hip", "corr_bank.hip", "corr_all.hip"), "SRCDSP_CORR_ALWAYS_EXACT",
                    os.path.join(TEST_BUILD, "libsrcdsp_hip_corr_exact.so")),
     "shared_dev": (("multi.hip",), "SRCDSP_TEST_SHARED_DEVICES", os.path.join(TEST_BUILD, "shared_dev", "libsrcdsp_hip.so")),
 }

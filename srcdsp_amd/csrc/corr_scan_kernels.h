@@ -36,19 +36,25 @@ __device__ __forceinline__ unsigned load_best(const unsigned *best) {
 // One tile (outputs tile * 4096 .. + 4095) of one channel's scan: `in`, `hist`,
 // `ptaps`, the carried registers and `best` are that channel's, all
 // block-uniform.  Dynamic LDS: corr_scan_lds_words(NP) words.
+// kAll (corr_all.hip's candidate pass): no early exit and no `best`; every
+// output is tested and each lane stores the 16-bit mask of its 16 outputs
+// (bit r: the test fires at output i0 + 16 t + r) at map[tile * kCBlock + t].
+template <bool kAll = false>
 __device__ __forceinline__ void corr_scan_tile(const uint32_t *__restrict__ in, long n,
                                                const uint32_t *__restrict__ hist,
                                                const uint32_t *__restrict__ ptaps, int N, int NP, unsigned cs,
                                                uint32_t c_prev0, uint32_t c_prev1, uint32_t e_prev0, unsigned *best,
-                                               long tile) {
+                                               long tile, uint16_t *__restrict__ map = nullptr) {
     extern __shared__ __attribute__((aligned(16))) uint32_t xs[];
     __shared__ uint32_t prev_c[kCBlock + 1][2], prev_e[kCBlock + 1];
     __shared__ unsigned dead_any, best0;
     constexpr int TO = kCBlock * kCR;
     const long i0 = tile * TO;  // first output of the tile
-    if (threadIdx.x == 0) best0 = load_best(best);
-    __syncthreads();
-    if ((long)best0 < i0) return;  // a hit before this tile is already known (block-uniform)
+    if constexpr (!kAll) {
+        if (threadIdx.x == 0) best0 = load_best(best);
+        __syncthreads();
+        if ((long)best0 < i0) return;  // a hit before this tile is already known (block-uniform)
+    }
     // taps front-padded with NP - N zero taps (NP = 16 ceil(N/16), as corr_eval_dot2)
     const int pad = NP - N;
     // tile sample l (input word i0 - (NP - 1) + l, l = 0 .. TO + NP - 2) -> LDS word
@@ -158,7 +164,7 @@ __device__ __forceinline__ void corr_scan_tile(const uint32_t *__restrict__ in, 
     bool dead = false;
     for (int m0 = 0, it = 0; m0 < NP; m0 += 16, ++it) {  // NP % 16 == 0
         chunk(m0);
-        if ((it & 15) == 15) {  // every 256 taps: has a hit before this tile been found?
+        if (!kAll && (it & 15) == 15) {  // every 256 taps: has a hit before this tile been found?
             const unsigned bb = __builtin_amdgcn_readfirstlane(load_best(best));
             if ((long)bb < i0) {
                 dead = true;
@@ -222,6 +228,7 @@ __device__ __forceinline__ void corr_scan_tile(const uint32_t *__restrict__ in, 
     uint32_t c_0 = 0, c_1 = 0, e_0 = 0;  // outputs 0 and 1, for the tests after the barrier
     uint32_t cm2 = 0, cm1 = 0, em1 = 0;  // the two outputs before r, the energy before r
     int hit = -1;                        // first hit among outputs 2..15 (lane-relative)
+    unsigned mask = 0;                   // kAll: every hit among the lane's outputs
 #pragma unroll
     for (int r = 0; r < kCR; ++r) {
         if (r > 0) {  // E_i = E_{i-1} + |x_i|^2 - |x_{i-N}|^2
@@ -235,6 +242,8 @@ __device__ __forceinline__ void corr_scan_tile(const uint32_t *__restrict__ in, 
             e_0 = ev;
         } else if (r == 1) {
             c_1 = c;
+        } else if constexpr (kAll) {
+            if (r < nrem && corr_hit(cm2, cm1, c, em1)) mask |= 1u << r;
         } else if (!dead && hit < 0 && r < nrem && corr_hit(cm2, cm1, c, em1)) {
             hit = r;
         }
@@ -249,6 +258,12 @@ __device__ __forceinline__ void corr_scan_tile(const uint32_t *__restrict__ in, 
     __syncthreads();
     if (dead_any) return;  // outputs past a known hit: nothing to record
     const uint32_t pc1 = prev_c[t][0], pc2 = prev_c[t][1], pe1 = prev_e[t];
+    if constexpr (kAll) {
+        if (1 < nrem && corr_hit(pc1, c_0, c_1, e_0)) mask |= 2u;
+        if (0 < nrem && corr_hit(pc2, pc1, c_0, pe1)) mask |= 1u;
+        map[tile * kCBlock + t] = (uint16_t)mask;
+        return;
+    }
     if (1 < nrem && corr_hit(pc1, c_0, c_1, e_0)) hit = 1;
     if (0 < nrem && corr_hit(pc2, pc1, c_0, pe1)) hit = 0;
     if (hit >= 0) atomicMin(best, (unsigned)(i0 + lb + hit));

@@ -774,6 +774,29 @@ class FixedPatternCorrelator(_Handle):
             A.call("srcdsp_corr_step_host", self._h, _ptr(x), n, C.byref(found), C.byref(idx))
         return bool(found.value), idx.value
 
+    def stepAll(self, inp, max_hits: int):
+        """Not a reference method: every detection the loop of step() on the
+        remainders makes in `inp`, at most `max_hits` of them, in one call.
+        Returns (indices, bits, consumed): the corrIndex of each detection
+        relative to `inp` (int array [k]), the bitSamples of each (int16
+        [k, N, 2]) and the samples the loop processed (< len(inp) only when
+        max_hits was reached; stepAll(inp[consumed:]) continues)."""
+        n, mh = _nsamples(inp, "ci16"), int(max_hits)
+        mh = min(mh, n // 2 + 1)  # detections lie at least two samples apart: no more rows are ever filled
+        k, used = C.c_int(0), C.c_size_t(0)
+        idx = np.zeros(max(mh, 1), np.intc)
+        bits = np.zeros((max(mh, 1), self.N, 2), np.int16)
+        ip, bp = idx.ctypes.data_as(A.IP), bits.ctypes.data_as(A.I16P)
+        if _is_device(inp):
+            A.call("srcdsp_corr_step_all", self._h, _ptr(inp), n, mh, C.byref(k), ip, bp, C.byref(used),
+                   _stream(inp))
+        else:
+            x = _host(inp, "ci16")
+            A.call("srcdsp_corr_step_all_host", self._h, _ptr(x), n, mh, C.byref(k), ip, bp, C.byref(used))
+        return idx[:k.value].copy(), bits[:k.value].copy(), used.value
+
+    step_all = stepAll
+
     def step_trace(self, inp):
         """step() as the reference's CREATE_DEBUG_FILES build runs it
         (correlators.h:253-257): (found, corrIndex, corr, energy), where corr[k]
@@ -841,6 +864,40 @@ def corr_step_batched(correlators, inp):
     found, idx = (C.c_int * ch)(), (C.c_int * ch)(*([-1] * ch))
     A.call("srcdsp_corr_step_batched", hs, ch, _ptr(inp), 0 if shared else n, n, found, idx, _stream(inp))
     return [(bool(found[c]), idx[c]) for c in range(ch)]
+
+
+def corr_step_all_batched(correlators, inp, max_hits: int):
+    """FixedPatternCorrelator.stepAll for C correlators in one call: channel c
+    is exactly ``correlators[c].stepAll(inp_c, max_hits)``.  ``inp`` as for
+    corr_step_batched: int16 [n, 2] (one shared input) or [C, n, 2], on the
+    device.  Returns a list of (indices, bits, consumed) per channel."""
+    ch, mh = len(correlators), int(max_hits)
+    if ch < 1:
+        raise ValueError("corr_step_all_batched: at least one correlator")
+    if not _is_device(inp):
+        raise TypeError("corr_step_all_batched() takes a device-resident buffer")
+    if inp.dim() not in (2, 3) or inp.shape[-1] != 2 or inp.element_size() != 2:
+        raise ValueError("corr_step_all_batched: inp is int16 [n, 2] (shared) or [C, n, 2]")
+    shared = inp.dim() == 2
+    if not shared and inp.shape[0] != ch:
+        raise ValueError("corr_step_all_batched: one input row per correlator")
+    n, N = inp.shape[-2], correlators[0].N
+    mh = min(mh, n // 2 + 1)  # detections lie at least two samples apart: no more rows are ever filled
+    hs = _handles(correlators)
+    k, used = (C.c_int * ch)(), (C.c_size_t * ch)()
+    idx = np.zeros((ch, max(mh, 1)), np.intc)
+    bits = np.zeros((ch, max(mh, 1), N, 2), np.int16)
+    A.call("srcdsp_corr_step_all_batched", hs, ch, _ptr(inp), 0 if shared else n, n, mh, k,
+           idx.ctypes.data_as(A.IP), bits.ctypes.data_as(A.I16P), used, _stream(inp))
+    return [(idx[c, :k[c]].copy(), bits[c, :k[c]].copy(), used[c]) for c in range(ch)]
+
+
+def corr_all_stats():
+    """(kernel_calls, loop_calls): stepAll calls served by the candidate and
+    resolve kernels and by the loop of srcdsp_corr_step, process-wide."""
+    b, l = C.c_ulong(), C.c_ulong()
+    A.call("srcdsp_corr_all_stats", C.byref(b), C.byref(l))
+    return b.value, l.value
 
 
 def corr_batched_stats():
