@@ -16,7 +16,8 @@
  * dsptl::QStagger is an extension with no reference class: the delay line on
  * the Q rail that makes the QPSK mapper's signal offset QPSK (the reference
  * leaves it to the application); srcdsp_modulate_offset_step(_batched) runs it
- * inside the transmit chain.
+ * inside the transmit chain.  dsptl::combineCarriers, an extension too, puts C
+ * carriers onto one wire (srcdsp_combine_step).
  *
  * Where the reference asserts (bits.size() against out.size(), :106 and :171)
  * the calls fail as the other drop-ins do (assert, or std::runtime_error
@@ -24,6 +25,8 @@
  */
 #ifndef SRCDSP_DROPIN_MODULATORS_H
 #define SRCDSP_DROPIN_MODULATORS_H
+
+#include <algorithm>
 
 #include "srcdsp_dropin_common.h"
 
@@ -115,6 +118,25 @@ public:
 private:
     srcdsp_stagger_t h_;
 };
+
+/// Extension (no reference call): C carriers onto one wire.  out[i] =
+/// limitScale<complex<int16_t>, complex<int32_t>>(sum_c rows[c][i], shift)
+/// (dsp_complex.h:83-108): the exact int32 sum, shifted right arithmetically
+/// and clamped to int16, per component.  1..65535 rows of one size, shift
+/// 0..15.  On device rows: srcdsp_combine_step.
+inline std::vector<std::complex<int16_t>> combineCarriers(const std::vector<std::vector<std::complex<int16_t>>> &rows,
+                                                          unsigned shift) {
+    srcdsp_detail::check_shape(!rows.empty(), "combineCarriers: no rows");
+    const size_t n = rows[0].size();
+    for (size_t c = 1; c < rows.size(); ++c)
+        srcdsp_detail::check_shape(rows[c].size() == n, "combineCarriers: the rows differ in size");
+    // the C ABI takes rows of one buffer
+    std::vector<std::complex<int16_t>> flat(rows.size() * n), out(n);
+    for (size_t c = 0; c < rows.size(); ++c) std::copy(rows[c].begin(), rows[c].end(), flat.begin() + c * n);
+    srcdsp_detail::check(srcdsp_combine_step_host(flat.data(), n, rows.size(), out.data(), n, shift),
+                         "combineCarriers");
+    return out;
+}
 
 }  // namespace dsptl
 #endif

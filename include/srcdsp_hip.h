@@ -404,6 +404,32 @@ SRCDSP_API int srcdsp_modulate_offset_stats(unsigned long *fused_calls, unsigned
                                             unsigned long *bank_calls, unsigned long *loop_calls);
 
 /* ============================================================================
+ * The carrier combiner: an extension with no reference call.  C carriers, each
+ * a row of complex<int16_t> as Mixer::step leaves it (mixers.h:169-188), onto
+ * one wire:
+ *   out[i] = limitScale<complex<int16_t>, complex<int32_t>>(
+ *                sum_{c < rows} in_c[i], shift)            (dsp_complex.h:83-108)
+ *   in_c = d_in + c*in_stride samples,  i < n
+ * The sum is exact in int32, then the arithmetic shift right by `shift` and the
+ * clamp to [-32768, 32767], each per component.  rows == 1 is limitScale(x,
+ * shift).
+ * ==========================================================================*/
+/* Extension (dsp_complex.h:83-108 over a sum of rows).  Stateless: no handle.
+ * rows is 1..65535 (rows * 32768 fits int32), shift 0..15, and neither buffer
+ * is null unless n == 0 (SRCDSP_ERR_ARG otherwise, before any HIP call).  n ==
+ * 0 does nothing.  in_stride == 0 sums the same row `rows` times.  Offsets are
+ * 64-bit: no INT_MAX limit on n or in_stride.  d_out may be row 0 itself (as
+ * the mixer runs in place); any other overlap of d_out with the rows is the
+ * caller's error and is not detected.  Rows whose base and stride are
+ * multiples of 16 bytes are read 16 bytes per lane; others sample by sample. */
+SRCDSP_API int srcdsp_combine_step(const void *d_in, size_t in_stride, size_t rows, void *d_out, size_t n,
+                                   unsigned shift, void *stream);
+/* Extension: the same on host buffers, with the kernel's own arithmetic on the
+ * host; no HIP call. */
+SRCDSP_API int srcdsp_combine_step_host(const void *in, size_t in_stride, size_t rows, void *out, size_t n,
+                                        unsigned shift);
+
+/* ============================================================================
  * FixedPatternCorrelator<int16_t, int32_t, N, S>   (correlators.h:54-316)
  * ==========================================================================*/
 typedef struct srcdsp_corr *srcdsp_corr_t;

@@ -91,6 +91,8 @@ SIGNATURES = {
     "srcdsp_modulate_offset_step": (I, [VP, VP, VP, VP, VP, SZ, VP, SZ, I, I, VP]),
     "srcdsp_modulate_offset_step_batched": (I, [HP, HP, HP, HP, I, VP, SZ, VP, SZ, SZ, I, VP]),
     "srcdsp_modulate_offset_stats": (I, [C.POINTER(C.c_ulong)] * 4),
+    "srcdsp_combine_step": (I, [VP, SZ, SZ, VP, SZ, U, VP]),
+    "srcdsp_combine_step_host": (I, [VP, SZ, SZ, VP, SZ, U]),
     "srcdsp_corr_create": (I, [HP, U, U]),
     "srcdsp_corr_destroy": (I, [VP]),
     "srcdsp_corr_clone": (I, [VP, HP]),

@@ -738,6 +738,64 @@ def modulate_offset_stats():
     return tuple(x.value for x in v)
 
 
+# ============================================================ carrier combiner
+def combine(rows, out=None, shift: int = 0):
+    """C carriers onto one wire (no reference call): ``out[i] =
+    limitScale(sum_c rows[c][i], shift)``, the exact int32 sum shifted right
+    arithmetically and clamped to int16, per component (dsp_complex.h:83-108).
+
+    ``rows``: an int16 device tensor [C, n, 2] (its rows may be a view ``[:, :n]``
+    of a wider buffer) or [n, 2] (one row), a list of [n, 2] device rows of one
+    buffer at one spacing, or the same as host arrays.  ``out``: int16 [n, 2];
+    it may be row 0 itself, and overlaps no other row.  Behind
+    ``modulate_offset_step_batched`` it puts the bank's carriers onto the one
+    row that ``mixdecim_step_batched`` takes as its shared input."""
+    shift = int(shift)
+    if isinstance(rows, (list, tuple)):
+        if not rows:
+            raise ValueError("combine: at least one row")
+        if _is_device(rows[0]):
+            n = _nsamples(rows[0], "ci16")
+            if any(not _is_device(r) or not r.is_contiguous() or str(r.dtype) != "torch.int16" or
+                   _nsamples(r, "ci16") != n for r in rows):
+                raise ValueError("combine: the rows are contiguous int16 device tensors [n, 2] of one size")
+            p = [r.data_ptr() for r in rows]
+            step = p[1] - p[0] if len(p) > 1 else 0
+            if step < 0 or step % 4 or any(b - a != step for a, b in zip(p, p[1:])):
+                raise ValueError("combine: the rows lie in one buffer, one whole number of samples apart")
+            first, ch, stride = rows[0], len(rows), step // 4
+        else:
+            rows = np.stack([_host(r, "ci16") for r in rows])
+    if not isinstance(rows, (list, tuple)):
+        if _is_device(rows):
+            t = rows if rows.dim() == 3 else rows.unsqueeze(0)
+            if t.dim() != 3 or t.shape[-1] != 2 or str(t.dtype) != "torch.int16" or t.shape[0] < 1:
+                raise ValueError("combine: rows is an int16 tensor [C, n, 2] or [n, 2]")
+            ch, n = t.shape[0], t.shape[1]
+            st = t.stride()
+            if n and (st[2] != 1 or (n > 1 and st[1] != 2) or (ch > 1 and (st[0] % 2 or st[0] < 0))):
+                raise ValueError("combine: samples are contiguous within a row, rows a whole number of samples apart")
+            first, stride = t[0], (st[0] // 2 if ch > 1 else 0)
+        else:
+            a = np.ascontiguousarray(rows, np.int16)
+            a = a.reshape((1,) + a.shape) if a.ndim == 2 else a
+            if a.ndim != 3 or a.shape[-1] != 2 or a.shape[0] < 1:
+                raise ValueError("combine: rows is int16 [C, n, 2] or [n, 2]")
+            if out is None:
+                out = np.zeros(a.shape[1:], np.int16)
+            if _is_device(out) or out.dtype != np.int16 or not out.flags.c_contiguous or out.size != 2 * a.shape[1]:
+                raise ValueError("combine: out is a contiguous int16 host array [n, 2]")
+            A.call("srcdsp_combine_step_host", _ptr(a), a.shape[1], a.shape[0], _ptr(out), a.shape[1], shift)
+            return out
+    if out is None:
+        out = _alloc_like(first, "ci16", n)
+    if not _is_device(out) or str(out.dtype) != "torch.int16" or not out.is_contiguous() or \
+            _nsamples(out, "ci16") != n:
+        raise ValueError("combine: out is a contiguous int16 device tensor [n, 2]")
+    A.call("srcdsp_combine_step", C.c_void_p(first.data_ptr()), stride, ch, _ptr(out), n, shift, _stream(out))
+    return out
+
+
 # ======================================================== FixedPatternCorrelator
 class FixedPatternCorrelator(_Handle):
     """dsptl::FixedPatternCorrelator<int16_t, int32_t, N, S> (correlators.h:54-316)."""
