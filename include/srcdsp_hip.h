@@ -429,6 +429,54 @@ SRCDSP_API int srcdsp_combine_step(const void *d_in, size_t in_stride, size_t ro
 SRCDSP_API int srcdsp_combine_step_host(const void *in, size_t in_stride, size_t rows, void *out, size_t n,
                                         unsigned shift);
 
+/* Extension.  C transmit chains from bits summed onto ONE wire in one call.
+ * d_out is one row of n_out complex<int16_t> and holds exactly what
+ *   srcdsp_modulate_offset_step_batched(mappers, ups, staggers, mixers, ...)
+ *     into C private rows (modulators.h:103-117 / :169-184,
+ *     upsampling_filters.h:149-233, the stagger, mixers.h:169-188; staggers ==
+ *     NULL: srcdsp_modulate_step_batched, the chains without a stagger), then
+ *   srcdsp_combine_step(rows, stride, channels, d_out, n_out, shift, stream)
+ *     (dsp_complex.h:83-108)
+ * would leave, without the [C, n_out] rows.  Every handle (mapper state,
+ * interpolator history, stagger carry, mixer phase) ends as the bank call
+ * leaves it, bit for bit.
+ * The bank's size and sharing rules apply (shared kind, variant, L, taps, D and
+ * N; every handle listed once; bits_stride 0 or >= n_bits; an odd QPSK n_bits
+ * is SRCDSP_ERR_SIZE).  n_out equals the bank's row length, L*(symbols +
+ * length/L when flushing), exactly (SRCDSP_ERR_SIZE otherwise); shift is 0..15
+ * and channels >= 1 (SRCDSP_ERR_ARG otherwise).  A refused call changes no
+ * handle; n_out == 0 does nothing.
+ * One kernel, a workgroup per tile of 2048 symbols looping over the chains with
+ * the sums in registers, exists for L = 2, 4 and 8 where the bank's one launch
+ * would serve the chains (variant 0 with int16-range taps, N <= 4096, D <= L,
+ * at L = 8 D = 4, d_bits 16-byte aligned, bits_stride a multiple of 16 bytes),
+ * with at most 64 chains and d_out 16-byte aligned.  It is routed by
+ * measurement (srcdsp_modulate_sum_geometry): as measured it serves L = 2 from
+ * 2048 tiles on with at most 8 chains, and no call at L = 4 or L = 8, where it
+ * did not beat the bank and the combiner at any length.  Every other call
+ * (those, L = 3, 5, 6 and 7, which have no kernel, more than 64 chains, D > L,
+ * int16-tap interpolators, unaligned bits, short rows) runs the bank into
+ * grow-only rows on the lead mapper and the combiner inside the call. */
+SRCDSP_API int srcdsp_modulate_sum_step(const srcdsp_mapper_t *mappers, const srcdsp_up_t *ups,
+                                        const srcdsp_stagger_t *staggers, const srcdsp_mixer_t *mixers, int channels,
+                                        const void *d_bits, size_t bits_stride, void *d_out, size_t n_out,
+                                        size_t n_bits, int flush, unsigned shift, void *stream);
+/* Extension.  Process-wide counters (the paths of modulators.h:103-184 ->
+ * upsampling_filters.h:149-233 -> stagger -> mixers.h:169-188 ->
+ * dsp_complex.h:83-108): calls served by the fused kernel / by the bank and the
+ * combiner */
+SRCDSP_API int srcdsp_modulate_sum_stats(unsigned long *fused_calls, unsigned long *bank_calls);
+/* Extension (routing of the sum behind mixers.h:169-188): the symbols one
+ * workgroup of the fused kernel covers, and the calls it serves of those it
+ * takes at interpolation by L: at least min_tiles tiles (0: none) and at most
+ * max_channels chains.  Null pointers are skipped. */
+SRCDSP_API int srcdsp_modulate_sum_geometry(unsigned L, int *tile_symbols, long *min_tiles, int *max_channels);
+/* Extension (routing of the sum behind mixers.h:169-188): min_tiles >= 1 routes
+ * every call the fused kernel takes (L = 2, 4 and 8, up to 64 chains) to it from
+ * that many tiles on, process-wide (tests, measurements); 0 puts the measured
+ * routing back; negative is SRCDSP_ERR_ARG.  Results do not depend on it. */
+SRCDSP_API int srcdsp_modulate_sum_set_min_tiles(long min_tiles);
+
 /* ============================================================================
  * FixedPatternCorrelator<int16_t, int32_t, N, S>   (correlators.h:54-316)
  * ==========================================================================*/

@@ -93,6 +93,10 @@ SIGNATURES = {
     "srcdsp_modulate_offset_stats": (I, [C.POINTER(C.c_ulong)] * 4),
     "srcdsp_combine_step": (I, [VP, SZ, SZ, VP, SZ, U, VP]),
     "srcdsp_combine_step_host": (I, [VP, SZ, SZ, VP, SZ, U]),
+    "srcdsp_modulate_sum_step": (I, [HP, HP, HP, HP, I, VP, SZ, VP, SZ, SZ, I, U, VP]),
+    "srcdsp_modulate_sum_stats": (I, [C.POINTER(C.c_ulong)] * 2),
+    "srcdsp_modulate_sum_geometry": (I, [U, IP, C.POINTER(C.c_long), IP]),
+    "srcdsp_modulate_sum_set_min_tiles": (I, [C.c_long]),
     "srcdsp_corr_create": (I, [HP, U, U]),
     "srcdsp_corr_destroy": (I, [VP]),
     "srcdsp_corr_clone": (I, [VP, HP]),

@@ -297,6 +297,7 @@ SRCDSP_API int srcdsp_mapper_destroy(srcdsp_mapper_t h) {
     }
     m.par.destroy();
     m.sym.destroy();
+    m.rows.destroy();
     if (m.stage.stream) m.stage.destroy();
     delete h;
     return SRCDSP_OK;

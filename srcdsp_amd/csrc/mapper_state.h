@@ -20,6 +20,7 @@ struct MapperState {
     int cur = 0;
     GrowBuf par{GrowBuf::kDevice};  // per-tile parities of the calls this handle led
     GrowBuf sym{GrowBuf::kDevice};  // srcdsp_modulate_*: packed SDPSK states, or the chain path's symbols
+    GrowBuf rows{GrowBuf::kDevice}; // srcdsp_modulate_sum_step: the carrier rows of the calls this handle led (bank path)
     Ordering order;
     HostStage stage;                // srcdsp_mapper_step_host
 

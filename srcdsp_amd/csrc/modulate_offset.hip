@@ -21,43 +21,11 @@
 // are those of the four calls, bit for bit.
 #include <algorithm>
 
-#include "modulate_kernels.h"
-#include "stagger_state.h"
+#include "modulate_offset_kernels.h"
 
 namespace srcdsp {
 namespace {
 PathCounter g_fused_calls, g_chain_calls, g_bank_calls, g_loop_calls;
-
-// the tile's stagger policy (STG of up_dot2_tile)
-struct UpQStagger {
-    static constexpr bool on = true;
-    int D;                    // 1..LR
-    const int16_t *carry_in;  // D values: the imaginary halves of the call's first D outputs
-    int16_t *carry_out;
-    uint16_t *slot;           // 8 values in LDS: the halves ahead of the tile's first word, the last D used
-
-    // lanes t < D, while the planes still hold the tile's input: value t of the
-    // D ahead of the tile, and of the D that end the call (its last tile only).
-    // tile_q(jr, o): clamped imaginary output of phase o of staged sample jr;
-    // halo: the staged index of the tile's first sample
-    template <int LR, class F>
-    __device__ __forceinline__ void seed(int t, long j0, long n_total, int halo, F &tile_q) const {
-        if (t >= D) return;
-        const int o = LR - D + t;
-        slot[8 - D + t] = j0 == 0 ? (uint16_t)carry_in[t] : (uint16_t)tile_q(halo - 1, o);
-        const long jl = n_total - 1 - j0;
-        if (jl < kUpRD * kUpBlockD) carry_out[t] = (int16_t)(uint16_t)tile_q(halo + (int)jl, o);
-    }
-    __device__ __forceinline__ uint4 seeds() const { return *(const uint4 *)slot; }
-};
-
-struct ModOffLaunch {
-    ModLaunch mod;
-    int D;
-    unsigned slot_off;  // byte offset of the seed slot in dynamic LDS
-    const int16_t *carry_in[kMaxBatch];
-    int16_t *carry_out[kMaxBatch];
-};
 
 template <int LR, int PPC>
 __global__ __launch_bounds__(kUpBlockD) void modoffset_tile_dot2(const ModOffLaunch A) {
@@ -96,50 +64,11 @@ int fused_launch(const srcdsp_mapper_t *maps, const srcdsp_up_t *ups, const srcd
                  const srcdsp_mixer_t *mixers, int nc, const void *d_bits, size_t bits_stride, void *d_out,
                  size_t out_stride, size_t n_bits, size_t n_sym, long n_total, bool iter, hipStream_t s) {
     srcdsp_up_state &u0 = ups[0]->u;
-    MapperState &lead = maps[0]->m;
     ModOffLaunch A{};
-    ModLaunch &Q = A.mod;
-    UpmixLaunch &P = Q.up;
-    A.D = (int)stags[0]->g.D;
-    Q.kind = lead.kind;
-    Q.bits = (const uint8_t *)d_bits;
-    Q.bits_stride = (long)bits_stride;
-    Q.n_bits = (long)n_bits;
-    if (Q.kind == MAPPER_SDPSK && n_bits) {
-        const size_t rw = pk_row_words(n_bits);
-        int rc = lead.sym.reserve(4 * rw * (size_t)nc);
-        if (!rc) rc = mapper_launch(lead, maps, nc, d_bits, bits_stride, lead.sym.d, rw, n_bits, kMapperStates, s);
-        if (rc) return rc;
-        Q.pk = lead.sym.dev<uint32_t>();
-        Q.pk_stride = (long)rw;
-    }
-    P.out = (uint32_t *)d_out;
-    P.pairs = u0.d_pair;
-    P.table = mixers[0]->m.d_table;
-    P.n_in = (long)n_sym;
-    P.n_total = n_total;
-    P.out_stride = (long)out_stride;
-    P.H = u0.H;
-    P.shift = iter ? 0u : (unsigned)(15 - u0.left_shift_factor);
-    P.N = mixers[0]->m.N;
-    const size_t tile_lds = up_dot2_smem(u0.H, u0.L);
-    P.tab_off = (unsigned)tile_lds;
-    A.slot_off = (unsigned)(tile_lds + ((2 * (size_t)P.N + 15) & ~(size_t)15));
-    const size_t smem = A.slot_off + 16;
-    const bool qpsk_state = Q.kind == MAPPER_QPSK && n_bits;
-    for (int c = 0; c < nc; ++c) {
-        MixerState &m = mixers[c]->m;
-        int rc = chan_begin(ups[c]->u, s, P.hist_in[c], P.hist_out[c]);
-        if (!rc) rc = m.order.before(s);
-        if (!rc) rc = stagger_begin(stags[c]->g, s, A.carry_in[c], A.carry_out[c]);
-        if (!rc && qpsk_state) {
-            MapperRowState row;
-            rc = mapper_begin(maps[c]->m, s, row);
-            Q.st_out[c] = row.out;
-        }
-        if (rc) return rc;
-        P.mix[c] = m.word();
-    }
+    size_t smem = 0;
+    int rc = modoff_launch_begin(A, maps, ups, stags, mixers, nc, d_bits, bits_stride, d_out, out_stride, n_bits, n_sym,
+                                 n_total, iter, s, &smem);
+    if (rc) return rc;
     constexpr int TI = kUpRD * kUpBlockD;
     const int PP = (u0.H + 1) / 2;
     const dim3 grid((unsigned)((n_total + TI - 1) / TI), (unsigned)nc);
@@ -169,19 +98,7 @@ int fused_launch(const srcdsp_mapper_t *maps, const srcdsp_up_t *ups, const srcd
     }
 #undef SRCDSP_MODOFF
     SRCDSP_HIP_TRY(hipGetLastError());
-    const unsigned long n_out = (unsigned long)u0.L * (unsigned long)n_total;
-    for (int c = 0; c < nc; ++c) {
-        MixerState &m = mixers[c]->m;
-        m.advance(n_out);
-        int rc = chan_commit(ups[c]->u, s);
-        if (!rc) rc = m.order.after(s);
-        if (!rc) rc = stagger_commit(stags[c]->g, s);
-        // SDPSK: the tile read the mapper's packed states, so the mapper's
-        // next step (which may rewrite them) is ordered after the tile too
-        if (!rc && n_bits) rc = qpsk_state ? mapper_commit(maps[c]->m, s) : maps[c]->m.order.after(s);
-        if (rc) return rc;
-    }
-    return SRCDSP_OK;
+    return modoff_launch_commit(maps, ups, stags, mixers, nc, n_bits, n_total, s);
 }
 
 // one checked chain of n_out > 0; *fused tells which path served it
@@ -250,28 +167,12 @@ SRCDSP_API int srcdsp_modulate_offset_step_batched(const srcdsp_mapper_t *mapper
     const char *who = "modulate_offset_step_batched";
     SRCDSP_ARG_CHECK(mappers != nullptr && ups != nullptr && staggers != nullptr && mixers != nullptr && channels >= 1,
                      "modulate_offset_step_batched: no handles");
-    int rc = check_handles(mappers, channels, who);
-    if (!rc) rc = check_handles(ups, channels, who);
-    if (!rc) rc = check_handles(staggers, channels, who);
-    if (!rc) rc = check_handles(mixers, channels, who);
+    size_t n_sym = 0, n_out = 0;
+    int rc = modulate_bank_check(mappers, ups, staggers, mixers, channels, n_bits, bits_stride, flush != 0, &n_sym,
+                                 &n_out, who);
     if (rc) return rc;
     const srcdsp_up_state &u0 = ups[0]->u;
     const MixerState &m0 = mixers[0]->m;
-    size_t n_sym = 0, n_out = 0;
-    rc = modulate_check(mappers[0]->m, u0, n_bits, &n_sym, &n_out, flush != 0, who);
-    if (rc) return rc;
-    for (int c = 1; c < channels; ++c) {
-        const srcdsp_up_state &uc = ups[c]->u;
-        SRCDSP_ARG_CHECK(mappers[c]->m.kind == mappers[0]->m.kind,
-                         "modulate_offset_step_batched: mappers must share a kind");
-        SRCDSP_ARG_CHECK(uc.variant == u0.variant && uc.L == u0.L && uc.h_raw == u0.h_raw,
-                         "modulate_offset_step_batched: interpolators must share variant, L and taps");
-        SRCDSP_ARG_CHECK(staggers[c]->g.D == staggers[0]->g.D,
-                         "modulate_offset_step_batched: staggers must share D");
-        SRCDSP_ARG_CHECK(mixers[c]->m.N == m0.N, "modulate_offset_step_batched: mixers must share N");
-    }
-    SRCDSP_ARG_CHECK(bits_stride == 0 || bits_stride >= n_bits,
-                     "modulate_offset_step_batched: bits_stride must be 0 (shared) or >= n_bits");
     if (out_stride < n_out) {
         set_error("modulate_offset_step_batched: out_stride must hold a row of L*(symbols + length/L when flushing) "
                   "samples");

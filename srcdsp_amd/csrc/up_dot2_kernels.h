@@ -2,7 +2,8 @@
 // (FilterUpsamplingFir, upsampling_filters.h:36-326), shared by upsamp.hip
 // (srcdsp_up_step) and upmix.hip (the interpolator -> mixer chain, which runs
 // the same tile with the mixer in its output epilogue); modulate.hip feeds it
-// from bits and modulate_offset.hip adds the OQPSK stagger ahead of the mixer.
+// from bits, modulate_offset.hip adds the OQPSK stagger ahead of the mixer and
+// modulate_sum.hip runs it once per chain without its store phase.
 #pragma once
 #include <string>
 
@@ -102,6 +103,49 @@ __device__ __forceinline__ void up_stagger_dispatch(int d, F &f) {
     }
 }
 
+// The store phase of a tile: the staged output tile in LDS (lane chunk of
+// 8 LR words at the padded stride, every wave's chunk written and a barrier
+// passed) -> whole-line 16-B stores of the tile's contiguous output.  Shared by
+// up_dot2_tile and by the kernels that stage words of their own
+// (modulate_sum.hip).
+template <int LR, bool NTS>
+__device__ __forceinline__ void up_tile_flush(uint4 *ob, int t, uint32_t *out, long j0, long n_total) {
+    constexpr int GPLo = kUpRD * LR / 4, STR = GPLo + 1;
+    const long wbase = (long)LR * j0;             // first output word of the tile
+    const long wend = (long)LR * n_total;         // output words of the call
+    // one whole ds_read_b128 per granule (volatile: the compiler split these
+    // reads into ds_read_b32 / ds_read2_b32 for the partial-tile branch, whose
+    // 32-lane groups at a 16-B stride hit 8 banks: 25 M conflict cycles per
+    // launch at L = 4, 2^26 inputs)
+    typedef uint32_t o4v_t __attribute__((ext_vector_type(4)));
+    typedef const volatile __attribute__((address_space(3))) o4v_t *lds_o4v;
+    auto oread = [&](int G) { return *(lds_o4v)(&ob[(G / GPLo) * STR + (G % GPLo)]); };
+    if (wbase + 4L * GPLo * kUpBlockD <= wend) {
+        // whole tile: every granule read, then every store issued, at one
+        // base address (no per-store range checks)
+        o4v_t v[GPLo];
+#pragma unroll
+        for (int i = 0; i < GPLo; ++i) v[i] = oread(i * kUpBlockD + t);
+        uint32_t *o = out + wbase + 4L * t;
+#pragma unroll
+        for (int i = 0; i < GPLo; ++i) {
+            if constexpr (NTS) {  // streaming store: the output is written once, 4L x the input bytes
+                __builtin_nontemporal_store(v[i], (o4v_t *)(o + 4 * i * kUpBlockD));
+            } else {
+                *(o4v_t *)(o + 4 * i * kUpBlockD) = v[i];
+            }
+        }
+        return;
+    }
+    for (int i = 0; i < GPLo; ++i) {  // the call's last, partial tile
+        const int G = i * kUpBlockD + t;          // output granule within the tile
+        const o4v_t vv4 = oread(G);
+        const long w0 = wbase + 4L * G;
+        for (int u = 0; u < 4; ++u)
+            if (w0 + u < wend) out[w0 + u] = vv4[u];
+    }
+}
+
 // One tile (blockIdx.x) of the call.
 // WS: window register sets (3: the next granule is read a chunk ahead, 150
 // VGPRs at LR = 4; 2: it is read at the end of the chunk into the set that
@@ -122,7 +166,10 @@ __device__ __forceinline__ void up_stagger_dispatch(int d, F &f) {
 // (tile 0) or the last phases of the sample before the tile, recomputed from
 // the halo the planes hold (D lanes, ceil(H/2) dot2 each; no workgroup waits
 // on another).  The same D lanes of the call's last tile write the new carry.
-template <int LR, bool NTS, int WS, int PPC, class EPI, class SRC, class STG = UpNoStagger>
+// STORE: false ends the tile behind the epilogue: nothing is staged or stored
+// and `out` is not used; the epilogue keeps what it was given (the summing
+// tile of modulate_sum.hip, which runs the tile once per chain).
+template <int LR, bool NTS, int WS, int PPC, class EPI, class SRC, class STG = UpNoStagger, bool STORE = true>
 __device__ __forceinline__ void up_dot2_tile(const SRC &src, long n_in, long n_total, const uint32_t *hist_in,
                                              uint32_t *hist_out, const uint32_t *pairs, int H, unsigned shift,
                                              uint32_t *out, EPI &epi, const STG &stg = STG()) {
@@ -355,7 +402,7 @@ __device__ __forceinline__ void up_dot2_tile(const SRC &src, long n_in, long n_t
                 }
                 w4[u] = epi(w);
             }
-            ob[t * STR + k] = make_uint4(w4[0], w4[1], w4[2], w4[3]);
+            if constexpr (STORE) ob[t * STR + k] = make_uint4(w4[0], w4[1], w4[2], w4[3]);
         }
     };
     if constexpr (STG::on) {
@@ -363,39 +410,9 @@ __device__ __forceinline__ void up_dot2_tile(const SRC &src, long n_in, long n_t
     } else {
         emit(std::integral_constant<int, 0>{});
     }
-    __syncthreads();
-    const long wbase = (long)LR * j0;             // first output word of the tile
-    const long wend = (long)LR * n_total;         // output words of the call
-    // one whole ds_read_b128 per granule (volatile: the compiler split these
-    // reads into ds_read_b32 / ds_read2_b32 for the partial-tile branch, whose
-    // 32-lane groups at a 16-B stride hit 8 banks: 25 M conflict cycles per
-    // launch at L = 4, 2^26 inputs)
-    typedef uint32_t o4v_t __attribute__((ext_vector_type(4)));
-    typedef const volatile __attribute__((address_space(3))) o4v_t *lds_o4v;
-    auto oread = [&](int G) { return *(lds_o4v)(&ob[(G / GPLo) * STR + (G % GPLo)]); };
-    if (wbase + 4L * GPLo * kUpBlockD <= wend) {
-        // whole tile: every granule read, then every store issued, at one
-        // base address (no per-store range checks)
-        o4v_t v[GPLo];
-#pragma unroll
-        for (int i = 0; i < GPLo; ++i) v[i] = oread(i * kUpBlockD + t);
-        uint32_t *o = out + wbase + 4L * t;
-#pragma unroll
-        for (int i = 0; i < GPLo; ++i) {
-            if constexpr (NTS) {  // streaming store: the output is written once, 4L x the input bytes
-                __builtin_nontemporal_store(v[i], (o4v_t *)(o + 4 * i * kUpBlockD));
-            } else {
-                *(o4v_t *)(o + 4 * i * kUpBlockD) = v[i];
-            }
-        }
-        return;
-    }
-    for (int i = 0; i < GPLo; ++i) {  // the call's last, partial tile
-        const int G = i * kUpBlockD + t;          // output granule within the tile
-        const o4v_t vv4 = oread(G);
-        const long w0 = wbase + 4L * G;
-        for (int u = 0; u < 4; ++u)
-            if (w0 + u < wend) out[w0 + u] = vv4[u];
+    if constexpr (STORE) {
+        __syncthreads();
+        up_tile_flush<LR, NTS>(ob, t, out, j0, n_total);
     }
 }
 

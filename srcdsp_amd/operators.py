@@ -796,6 +796,62 @@ def combine(rows, out=None, shift: int = 0):
     return out
 
 
+# ===================================================== summing modulator bank
+def modulate_sum_step(mappers, ups, staggers, mixers, bits, out=None, shift: int = 0, flush: bool = False):
+    """C transmit chains from bits onto one wire in one call: ``out`` is what
+    ``modulate_offset_step_batched`` into C rows (``staggers=None``:
+    ``modulate_step_batched``) and ``combine(rows, out, shift)`` leave, and every
+    handle ends as the bank leaves it, without the [C, n_out] rows.  ``bits``
+    [n] is shared, [C, n] one row per channel (its rows may be a view ``[:, :n]``
+    of a wider buffer); ``out`` is int16 [L*(symbols + length/L when flushing),
+    2], made when None.  Device tensors."""
+    ch = len(mappers)
+    if ch < 1 or len(ups) != ch or len(mixers) != ch or (staggers is not None and len(staggers) != ch):
+        raise ValueError("summing modulator bank: one mapper, interpolator, stagger (or None for all) and mixer per "
+                         "channel, at least one channel")
+    shared, n = _bank_bits(bits, ch, "summing modulator bank")
+    stride = 0
+    if not shared:
+        if (n and bits.stride(1) != 1) or (ch > 1 and bits.stride(0) < n):
+            raise ValueError("summing modulator bank: bits are contiguous within a row, rows at least n apart")
+        stride = bits.stride(0) if ch > 1 else n
+    if out is None:
+        up = ups[0]
+        extra = up.L * (up.getLength() // up.L) if flush else 0
+        out = _alloc_like(bits, "ci16", mappers[0].n_out(n) * up.L + extra)
+    if not _is_device(out) or str(out.dtype) != "torch.int16" or not out.is_contiguous():
+        raise ValueError("summing modulator bank: out is a contiguous int16 device tensor [n_out, 2]")
+    A.call("srcdsp_modulate_sum_step", _handles(mappers), _handles(ups),
+           _handles(staggers) if staggers is not None else None, _handles(mixers), ch, C.c_void_p(bits.data_ptr()),
+           stride, _ptr(out), _nsamples(out, "ci16"), n, int(flush), int(shift), _stream(bits))
+    return out
+
+
+def modulate_sum_stats():
+    """(fused_calls, bank_calls): summing modulator calls served by the fused
+    kernel and by the bank followed by the combiner, process-wide."""
+    v = [C.c_ulong() for _ in range(2)]
+    A.call("srcdsp_modulate_sum_stats", *[C.byref(x) for x in v])
+    return tuple(x.value for x in v)
+
+
+def modulate_sum_geometry(L: int):
+    """(tile_symbols, min_tiles, max_channels): the symbols one workgroup of the
+    fused kernel covers, and the calls it serves of those it takes at
+    interpolation by L: at least min_tiles tiles (0: none), at most
+    max_channels chains."""
+    t, a, b = C.c_int(), C.c_long(), C.c_int()
+    A.call("srcdsp_modulate_sum_geometry", int(L), C.byref(t), C.byref(a), C.byref(b))
+    return t.value, a.value, b.value
+
+
+def modulate_sum_set_min_tiles(min_tiles: int):
+    """Route every call the fused kernel takes to it from ``min_tiles`` tiles
+    on, process-wide (tests, measurements); 0 puts the measured routing back.
+    Results do not depend on the routing."""
+    A.call("srcdsp_modulate_sum_set_min_tiles", int(min_tiles))
+
+
 # ======================================================== FixedPatternCorrelator
 class FixedPatternCorrelator(_Handle):
     """dsptl::FixedPatternCorrelator<int16_t, int32_t, N, S> (correlators.h:54-316)."""
