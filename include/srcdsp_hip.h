@@ -245,6 +245,56 @@ SRCDSP_API int srcdsp_upmix_step_batched(const srcdsp_up_t *ups, const srcdsp_mi
 SRCDSP_API int srcdsp_upmix_stats(unsigned long *fused_calls, unsigned long *pair_calls,
                                   unsigned long *bank_calls, unsigned long *loop_calls);
 
+/* FilterUpsamplingFir (variant 0 or 1) -> FilterDnsamplingFir (variant 1 or 2),
+ * the rational L/M rate change: the two reference calls up.step(in, tmp,
+ * flush) (the vector overload, upsampling_filters.h:149-233: shift 15 -
+ * round(log2 L), asymmetric clamp to int16, dsp_complex.h:83-108) and
+ * decim.step(tmp, out) (dnsampling_filters.h:129-172: shift coeffScaling -
+ * leftShift masked & 31, symmetric +-32767 clamp, dsp_complex.cpp:63-73) in one
+ * call; the caller never allocates tmp.  With n_mid = L*(n_in + (flush ?
+ * length/L : 0)): n_mid % M == 0 and n_out == n_mid / M, else SRCDSP_ERR_SIZE;
+ * n_in == 0 without flush is SRCDSP_OK and changes nothing.  Both handles end
+ * as the two calls leave them (the interpolator's history as srcdsp_up_step
+ * writes it, the decimator's the last N_d - 1 interpolated samples of history
+ * ++ call; coeffScaling and leftShift untouched), so any later
+ * single-operator or fused call on either handle continues bit for bit.
+ * Interpolator variant 2 (real int16_t) and decimator variants 0 and 3 cannot
+ * be chained: SRCDSP_ERR_UNSUPPORTED.  Null handle: SRCDSP_ERR_ARG.  A refused
+ * call changes no handle.  The iterator overload (shift 0) is not offered.
+ * One kernel (resample_tile_dot2) takes interpolator variant 0 with int16-range
+ * taps, L = 2..8, <= 4096 taps, decimator variant 1 with int16-range taps, M =
+ * 1..8, <= 1024 taps, and 16-byte aligned d_in and d_out; of those it serves
+ * the shape classes where it measured faster than the two calls (DESIGN 5.4c:
+ * L/M = 4/3 and 2/3 in calls of at least 2048 tiles of 2048 inputs, rows x
+ * tiles per row).
+ * Every other call runs srcdsp_up_step into a grow-only scratch owned by the
+ * interpolator handle and srcdsp_decim_step from it. */
+SRCDSP_API int srcdsp_resample_step(srcdsp_up_t up, srcdsp_decim_t decim, const void *d_in, size_t n_in,
+                                    void *d_out, size_t n_out, int flush, void *stream);
+/* Extension (no reference call).  C such chains in one call: channel c reads
+ * d_in + c*in_stride samples and writes the row d_out + c*out_stride samples
+ * exactly as srcdsp_resample_step(ups[c], decims[c], ...) would.  in_stride >=
+ * n_in (there is no shared-input form: equal filters on one input give equal
+ * rows); out_stride >= n_out (SRCDSP_ERR_SIZE otherwise).  The interpolators
+ * must share variant, L and taps, the decimators variant, M, taps, flags and
+ * shift; every handle is listed once; channels >= 1 (SRCDSP_ERR_ARG otherwise,
+ * before anything is enqueued).  One launch (grid.y = channel, 64 per launch)
+ * where the single call's kernel serves and both row strides are multiples of
+ * 16 bytes; otherwise the call loops the single call. */
+SRCDSP_API int srcdsp_resample_step_batched(const srcdsp_up_t *ups, const srcdsp_decim_t *decims, int channels,
+                                            const void *d_in, size_t in_stride, void *d_out, size_t out_stride,
+                                            size_t n_in, int flush, void *stream);
+/* process-wide counters: single calls served by the fused kernel / by the pair
+ * of operators, batched calls served by one launch / by the per-channel loop */
+SRCDSP_API int srcdsp_resample_stats(unsigned long *fused_calls, unsigned long *pair_calls,
+                                     unsigned long *bank_calls, unsigned long *loop_calls);
+/* the fused kernel's tile (input samples) and its decimator tap limit */
+SRCDSP_API int srcdsp_resample_geometry(int *tile_inputs, int *max_decim_taps);
+/* Test and measurement hook: min_tiles >= 1 sends every call the fused kernel
+ * takes with at least that many tiles to it, whatever was measured; 0 restores
+ * the measured routing.  Process-wide. */
+SRCDSP_API int srcdsp_resample_set_min_tiles(long min_tiles);
+
 /* ============================================================================
  * SymbolMapperSdpsk<int16_t> (modulators.h:82-131) and
  * SymbolMapperQpsk<int16_t>  (modulators.h:147-198)

@@ -66,6 +66,11 @@ SIGNATURES = {
     "srcdsp_upmix_step": (I, [VP, VP, VP, SZ, VP, SZ, I, I, VP]),
     "srcdsp_upmix_step_batched": (I, [HP, HP, I, VP, SZ, VP, SZ, SZ, I, VP]),
     "srcdsp_upmix_stats": (I, [C.POINTER(C.c_ulong)] * 4),
+    "srcdsp_resample_step": (I, [VP, VP, VP, SZ, VP, SZ, I, VP]),
+    "srcdsp_resample_step_batched": (I, [HP, HP, I, VP, SZ, VP, SZ, SZ, I, VP]),
+    "srcdsp_resample_stats": (I, [C.POINTER(C.c_ulong)] * 4),
+    "srcdsp_resample_geometry": (I, [IP, IP]),
+    "srcdsp_resample_set_min_tiles": (I, [C.c_long]),
     "srcdsp_mapper_create": (I, [HP, I]),
     "srcdsp_mapper_destroy": (I, [VP]),
     "srcdsp_mapper_clone": (I, [VP, HP]),

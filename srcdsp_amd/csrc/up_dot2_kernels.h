@@ -2,8 +2,9 @@
 // (FilterUpsamplingFir, upsampling_filters.h:36-326), shared by upsamp.hip
 // (srcdsp_up_step) and upmix.hip (the interpolator -> mixer chain, which runs
 // the same tile with the mixer in its output epilogue); modulate.hip feeds it
-// from bits, modulate_offset.hip adds the OQPSK stagger ahead of the mixer and
-// modulate_sum.hip runs it once per chain without its store phase.
+// from bits, modulate_offset.hip adds the OQPSK stagger ahead of the mixer,
+// modulate_sum.hip runs it once per chain without its store phase and
+// resample.hip puts the decimator behind it in place of that phase.
 #pragma once
 #include <string>
 
@@ -30,6 +31,9 @@ struct srcdsp_up_state {
     int cur = 0;
     Ordering order;
     HostStage stage;
+    // the interpolated stream between the two launches of an unfused
+    // interpolator -> decimator call (resample.hip)
+    GrowBuf mid{GrowBuf::kDevice};
 };
 
 // sample j of the virtual stream (history ++ input ++ flush zeros), as a packed word
@@ -90,6 +94,12 @@ struct UpStoreEpilogue {
 // no stagger between the clamp and the epilogue: the tile as upsamp.hip,
 // upmix.hip and modulate.hip run it
 struct UpNoStagger {
+    static constexpr bool on = false;
+};
+
+// no deeper halo and no second stage behind the tile: every kernel but the
+// resampler's (resample_kernels.h)
+struct UpNoHalo {
     static constexpr bool on = false;
 };
 
@@ -169,15 +179,30 @@ __device__ __forceinline__ void up_tile_flush(uint4 *ob, int t, uint32_t *out, l
 // STORE: false ends the tile behind the epilogue: nothing is staged or stored
 // and `out` is not used; the epilogue keeps what it was given (the summing
 // tile of modulate_sum.hip, which runs the tile once per chain).
-template <int LR, bool NTS, int WS, int PPC, class EPI, class SRC, class STG = UpNoStagger, bool STORE = true>
+// HALO: the planes are staged halo.HG granules deep instead of ceil(PP/4), and
+// once they are staged halo.fill(t, j0, 8 HG, tile_w) runs, tile_w(jr, o) being
+// the clamped output word of phase o of staged sample jr (counted from the
+// planes' first sample; jr >= 2 PP) computed on the calling lane (UpNoHalo:
+// neither; the resampler's decimator stage, resample_kernels.h, which needs
+// the interpolated words before the tile).
+template <int LR, bool NTS, int WS, int PPC, class EPI, class SRC, class STG = UpNoStagger, bool STORE = true,
+          class HALO = UpNoHalo>
 __device__ __forceinline__ void up_dot2_tile(const SRC &src, long n_in, long n_total, const uint32_t *hist_in,
                                              uint32_t *hist_out, const uint32_t *pairs, int H, unsigned shift,
-                                             uint32_t *out, EPI &epi, const STG &stg = STG()) {
+                                             uint32_t *out, EPI &epi, const STG &stg = STG(),
+                                             const HALO &halo = HALO()) {
     constexpr int R = kUpRD, TI = R * kUpBlockD;
     extern __shared__ uint4 ug[];  // 4 planes (E_re, E_im, O_re, O_im) of PGR granules each
     const int Hm1 = H - 1;
     const int PP = PPC ? PPC : (H + 1) / 2;  // pairs per phase
-    const int HG = (PP + 3) / 4;         // halo granules per plane (window reach: dword D0 - PP)
+    // halo granules per plane (window reach: dword D0 - PP)
+    const int HG = [&] {
+        if constexpr (HALO::on) {
+            return halo.HG;
+        } else {
+            return (PP + 3) / 4;
+        }
+    }();
     const int PGR = TI / 8 + HG;         // granules per plane (4 dwords = 8 samples)
     const int t = threadIdx.x;
     // sample j of the virtual stream (history ++ input ++ flush zeros)
@@ -253,6 +278,22 @@ __device__ __forceinline__ void up_dot2_tile(const SRC &src, long n_in, long n_t
             return limit_t16_pair(0, acc, shift) >> 16;
         };
         stg.template seed<LR>(t, j0, n_total, 8 * HG, tile_q);
+    }
+    if constexpr (HALO::on) {
+        // as tile_q, both components: pair p on dwords m - p of planes E_re /
+        // E_im (jr = 2m + 1) or m - 1 - p of planes O_re / O_im (jr = 2m)
+        auto tile_w = [&](int jr, int o) -> uint32_t {
+            const uint32_t *pr = pl + ((jr & 1) ? (jr >> 1) : 2 * PDW + (jr >> 1) - 1), *pi = pr + PDW;
+            int32_t ar = 0, ai = 0;
+#pragma unroll 8  // 8 tap and 16 plane loads in flight
+            for (int p = 0; p < PP; ++p) {
+                const short2_t_u c = __builtin_bit_cast(short2_t_u, pairs[p * LR + o]);
+                ar = __builtin_amdgcn_sdot2(__builtin_bit_cast(short2_t_u, pr[-p]), c, ar, false);
+                ai = __builtin_amdgcn_sdot2(__builtin_bit_cast(short2_t_u, pi[-p]), c, ai, false);
+            }
+            return limit_t16_pair(ar, ai, shift);
+        };
+        halo.fill(t, j0, 8 * HG, tile_w);
     }
     // lane base: input j0 + 8t = plane dword D0 = 4t + 4*HG (granule gb).  Input
     // r, pair p reads dword D0 + k - p, k = r/2 - 1 in plane O for even r,

@@ -416,6 +416,7 @@ SRCDSP_API int srcdsp_up_destroy(srcdsp_up_t h) {
         if (h->u.d_hist[b]) (void)hipFree(h->u.d_hist[b]);
     h->u.order.destroy();
     h->u.stage.destroy();
+    h->u.mid.destroy();
     delete h;
     return SRCDSP_OK;
 }

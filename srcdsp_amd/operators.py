@@ -483,6 +483,75 @@ def upmix_stats():
     return tuple(x.value for x in v)
 
 
+class RationalResampler:
+    """up.step(in, tmp, flush); decim.step(tmp, out) in one call: the L/M rate
+    change.  Both operators' state advances exactly as the two calls; ``tmp``
+    is never the caller's.  ``out`` holds exactly L*n/M samples (L*(n +
+    length/L)/M with flush), which must be whole.  Device tensors only."""
+
+    def __init__(self, up: FilterUpsamplingFir, decim: FilterDnsamplingFir):
+        self.up, self.decim = up, decim
+
+    def step(self, inp, out=None, flush: bool = False):
+        if not _is_device(inp):
+            raise ValueError("RationalResampler: device tensors only")
+        n = _nsamples(inp, "ci16")
+        if out is None:
+            n_mid = self.up.L * (n + (self.up.getLength() // self.up.L if flush else 0))
+            if n_mid % self.decim.M:
+                raise ValueError("RationalResampler: L*(n + length/L when flushing) must be a multiple of M")
+            out = _alloc_like(inp, "ci16", n_mid // self.decim.M)
+        A.call("srcdsp_resample_step", self.up._h, self.decim._h, _ptr(inp), n, _ptr(out), _nsamples(out, "ci16"),
+               int(flush), _stream(inp))
+        return out
+
+
+def resample_step_batched(ups, decims, inp, out, flush: bool = False):
+    """Step C interpolator -> decimator chains in one call: channel c is exactly
+    ``RationalResampler(ups[c], decims[c]).step``.  ``inp`` is [C, n, 2], one
+    row per channel; ``out`` is [C, >= L*(n + length/L when flushing)/M, 2],
+    columns past a row's samples are left untouched.  Device tensors of
+    complex<int16_t> samples (int16 [..., 2]); rows may be views of wider
+    tensors (the row stride is taken from the tensor)."""
+    ch = len(ups)
+    if ch < 1 or len(decims) != ch:
+        raise ValueError("resampler bank: need one decimator per interpolator, at least one channel")
+    if not (_is_device(inp) and _is_device(out)):
+        raise ValueError("resampler bank: device tensors only")
+    if inp.dim() != 3 or inp.shape[-1] != 2 or out.dim() != 3 or out.shape[-1] != 2:
+        raise ValueError("resampler bank: inp is int16 [C, n, 2], out int16 [C, L*(n + flush)/M, 2]")
+    if inp.shape[0] != ch or out.shape[0] != ch:
+        raise ValueError("resampler bank: one input row and one output row per channel")
+    for x in (inp, out):
+        if x.stride(2) != 1 or x.stride(1) != 2 or x.stride(0) % 2:
+            raise ValueError("resampler bank: rows of contiguous samples")
+    A.call("srcdsp_resample_step_batched", _handles(ups), _handles(decims), ch, C.c_void_p(inp.data_ptr()),
+           inp.stride(0) // 2, C.c_void_p(out.data_ptr()), out.stride(0) // 2, inp.shape[1], int(flush), _stream(inp))
+    return out
+
+
+def resample_stats():
+    """(fused_calls, pair_calls, bank_calls, loop_calls): single resampler calls
+    served by the fused kernel and by the pair of operators, batched calls
+    served by one launch and by the per-channel loop, process-wide."""
+    v = [C.c_ulong() for _ in range(4)]
+    A.call("srcdsp_resample_stats", *[C.byref(x) for x in v])
+    return tuple(x.value for x in v)
+
+
+def resample_geometry():
+    """(tile_inputs, max_decim_taps) of the fused resampler kernel."""
+    a, b = C.c_int(), C.c_int()
+    A.call("srcdsp_resample_geometry", C.byref(a), C.byref(b))
+    return a.value, b.value
+
+
+def resample_set_min_tiles(min_tiles: int):
+    """Test and measurement hook: send every call the fused resampler kernel
+    takes with at least ``min_tiles`` tiles to it (0: the measured routing)."""
+    A.call("srcdsp_resample_set_min_tiles", int(min_tiles))
+
+
 # ================================================================ symbol mappers
 def _bits(x):
     """Bits as the reference takes them: one uint8_t each, a one when non-zero."""
