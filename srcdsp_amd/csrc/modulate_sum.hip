@@ -209,10 +209,17 @@ int launch_one(const ModOffLaunch &A, int nc, unsigned shift, void *d_out, unsig
 template <int LR, bool STG>
 int launch_pp(const ModOffLaunch &A, int PP, int nc, unsigned shift, void *d_out, unsigned tiles, size_t smem,
               hipStream_t s) {
-    // the compile-time shapes of up_tile_dot2: 16, 32 or 64 taps per phase
+    // the compile-time shapes of up_tile_dot2: 16, 32 or 64 taps per phase.  L = 8
+    // has 16 only: modsum_tile_dot2<8, 16, *> gave a wrong wire on hardware
+    // (tests/test_gpu_modulate_sum_sweep.py at 31 and 32 taps per phase, with and
+    // without staggers; the same with its first pair through the builtin, so not
+    // the inline v_dot2), where every other instantiation and the run-time kernel
+    // on the same shapes equal the model, so these run the run-time kernel
     switch (PP) {
     case 8: return launch_one<LR, 8, STG>(A, nc, shift, d_out, tiles, smem, s);
-    case 16: return launch_one<LR, 16, STG>(A, nc, shift, d_out, tiles, smem, s);
+    case 16:
+        if constexpr (LR < 8) return launch_one<LR, 16, STG>(A, nc, shift, d_out, tiles, smem, s);
+        break;
     case 32:
         if constexpr (LR < 8) return launch_one<LR, 32, STG>(A, nc, shift, d_out, tiles, smem, s);
         break;

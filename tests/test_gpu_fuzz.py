@@ -15,10 +15,22 @@ iterator form, retunes, resets, copies, the fused call and the separate
 operators taking turns on the same handles, inputs off 16-byte alignment, and
 banks of 1 to 65 rows at any strides; after every call every output byte and
 every state, the guard band behind every row, and the path counter the
-documented dispatch rule predicts.  The draws are tests/tx_fuzz_draw.py's."""
+documented dispatch rule predicts.  The draws are tests/tx_fuzz_draw.py's.
+
+The rational resampler (srcdsp_resample_*) is fuzzed the same way against the
+oracle's interpolator and decimator in sequence, under
+resample_set_min_tiles(1): L, M, taps per phase and decimator taps on and off
+what the fused kernel takes, legal ragged steps, flushes, the fused call and
+the two single operators taking turns on the same handles, inputs off 16-byte
+alignment, new left shifts, resets, copies, and banks of 1 to 65 rows at any
+strides; after every call every output sample, the decimator's state, the
+interpolator's next call on a copy, the guard band and the path counter the
+dispatch rule predicts.  The draws are tests/resample_fuzz_draw.py's
+(tests/test_resample_fuzz_draw.py holds them to their conditions)."""
 import numpy as np
 import pytest
 
+import resample_fuzz_draw as R
 import tx_fuzz_draw as F
 from tx_chain_model import UPMIX, TxChain
 
@@ -431,3 +443,178 @@ def test_fuzz_transmit_bank(S, O, seed):
         for r, (g, m) in enumerate(ps):
             assert got[r, :n_out].tobytes() == exps[r].tobytes(), (what, k, r)
             assert g.state() == m.state(), (what, k, r)
+
+
+# --- the rational resampler: the fused interpolator -> decimator call, single and banks ---
+
+_RS_GUARD, _RS_GUARD_VALUE = 24, 0x5A5A
+
+
+class _RsModel:
+    """The oracle's two calls with what fixes their state, so that a copy can
+    be rebuilt: the interpolator with its last inputs (tx_chain_model._Up), the
+    decimator with its left shift and the last N_d - 1 interpolated samples."""
+
+    def __init__(self, o, sh, up=None, ls=None, tail=None):
+        from tx_chain_model import _Up
+        self.o, self.sh = o, sh
+        self.up = _Up(o, sh["uvar"], sh["L"], sh["cu"]) if up is None else up
+        self.dec = o.decim(sh["dvar"], sh["M"], sh["cd"])
+        self.ls = sh["ls"] if ls is None else ls
+        self.dec.set_left_shift(self.ls)
+        self.tail = np.zeros((sh["Nd"] - 1, 2), np.int16)
+        if tail is not None and len(tail):  # whole blocks of M ending in the tail: the outputs are dropped
+            self.dec.step(np.concatenate([np.zeros(((-len(tail)) % sh["M"], 2), np.int16), tail]))
+            self.tail = tail.copy()
+
+    def copy(self):
+        return _RsModel(self.o, self.sh, self.up.copy(), self.ls, self.tail)
+
+    def set_left_shift(self, ls):
+        self.ls = ls
+        self.dec.set_left_shift(ls)
+
+    def reset_up(self):
+        self.up.reset()
+
+    def reset_decim(self):
+        self.dec.reset()
+        self.tail[:] = 0
+
+    def step(self, x, flush=False):
+        mid = self.up.step(x, flush, False)
+        fed = np.concatenate([self.tail, mid])
+        self.tail = fed[len(fed) - (self.sh["Nd"] - 1):].copy()
+        return self.dec.step(mid)
+
+    def same_decim_state(self, dec, what):
+        """As the handle reports it."""
+        st = dec.state()
+        assert st["coeff_scaling"] == self.dec.coeff_scaling and st["left_shift"] == self.ls, what
+        assert st["history"].tobytes() == self.tail.tobytes(), what
+
+    def same_up_state(self, up, probe, what):
+        """The interpolator's history, as a further step of copies shows it."""
+        import copy
+        got = copy.copy(up).step(_dev(probe)).cpu().numpy()
+        assert got.tobytes() == self.up.copy().step(probe, False, False).tobytes(), what
+
+
+class _RsGpu:
+    def __init__(self, S, sh):
+        cu = sh["cu"].astype(np.int16) if sh["uvar"] == 1 else sh["cu"]
+        cd = sh["cd"].astype(np.int16) if sh["dvar"] == 2 else sh["cd"]
+        self.up = S.FilterUpsamplingFir(cu, sh["L"], *_UP_T[sh["uvar"]])
+        self.dec = S.FilterDnsamplingFir(cd, sh["M"], *_DECIM_T[sh["dvar"]])
+        self.dec.set_left_shift(sh["ls"])
+
+    def copy(self):
+        import copy
+        c = object.__new__(_RsGpu)
+        c.up, c.dec = copy.copy(self.up), copy.copy(self.dec)
+        return c
+
+    def set_left_shift(self, ls):
+        self.dec.set_left_shift(ls)
+
+    def reset_up(self):
+        self.up.reset()
+
+    def reset_decim(self):
+        self.dec.reset()
+
+
+@pytest.fixture
+def resample_every_tile_count(S):
+    """The fused resampler kernel serves whatever it takes, however short."""
+    S.resample_set_min_tiles(1)
+    yield
+    S.resample_set_min_tiles(0)
+
+
+def _rs_what(seed, sh):
+    return (seed, sh["L"], sh["H"], sh["M"], sh["Nd"], sh["uvar"], sh["dvar"], sh["taps_kind"])
+
+
+@pytest.mark.parametrize("seed", range(R.CHAIN_SEEDS))
+def test_fuzz_resample_chain(S, O, resample_every_tile_count, seed):
+    import torch
+    from tx_gpu import dev, dev_off
+    rng = R.chain_rng(seed)
+    sh = R.draw_shape(rng)
+    ops = R.draw_ops(rng, sh)
+    g, m = _RsGpu(S, sh), _RsModel(O["strict"], sh)
+    what = _rs_what(seed, sh)
+    probe = R.draw_input(rng, 40)
+    for k, op in enumerate(ops):
+        if op[0] == "copy":  # go on with copies of both handles
+            g, m = g.copy(), m.copy()
+            continue
+        if op[0] != "step":
+            getattr(g, op[0])(*op[1:])
+            getattr(m, op[0])(*op[1:])
+            continue
+        a = op[1]
+        x = R.draw_input(rng, a["n"])
+        xd = dev_off(x) if a["off"] else dev(x)
+        exp = m.step(x, a["flush"])
+        s0 = S.resample_stats()
+        if a["fused"]:
+            buf = torch.full((len(exp) + _RS_GUARD, 2), _RS_GUARD_VALUE, dtype=torch.int16, device="cuda")
+            S.RationalResampler(g.up, g.dec).step(xd, buf[:len(exp)], a["flush"])
+            got = buf.cpu().numpy()
+            assert (got[len(exp):] == _RS_GUARD_VALUE).all(), (what, k, a)
+            got = got[:len(exp)]
+        else:
+            got = g.dec.step(g.up.step(xd, None, a["flush"])).cpu().numpy()
+        rose = tuple(b - c for c, b in zip(s0, S.resample_stats()))
+        if not a["fused"] or len(exp) == 0:
+            assert rose == (0, 0, 0, 0), (what, k, a, rose)
+        else:  # the fused kernel where the dispatch rule says so, else the pair
+            assert rose == _one_hot(0 if R.eligible(sh) and not a["off"] else 1), (what, k, a, rose)
+        assert got.shape == exp.shape and got.tobytes() == exp.tobytes(), (what, k, a)
+        m.same_decim_state(g.dec, (what, k, a))
+        m.same_up_state(g.up, probe, (what, k, a))
+
+
+@pytest.mark.parametrize("seed", range(R.BANK_SEEDS))
+def test_fuzz_resample_bank(S, O, resample_every_tile_count, seed):
+    import torch
+    from tx_gpu import dev
+    rng = R.bank_rng(seed)
+    sh = R.draw_bank(rng)
+    rows = sh["rows"]
+    what = _rs_what(seed, sh) + (rows,)
+    ps = []
+    for r in range(rows):  # every row its own histories
+        g, m = _RsGpu(S, sh), _RsModel(O["strict"], sh)
+        x = R.draw_input(rng, sh["g"] * int(rng.integers(1, 12)))
+        assert g.dec.step(g.up.step(dev(x))).cpu().numpy().tobytes() == m.step(x).tobytes(), (what, r)
+        ps.append((g, m))
+    ups, decs = [g.up for g, _ in ps], [g.dec for g, _ in ps]
+    probe = R.draw_input(rng, 40)
+    for k, (n, flush) in enumerate(sh["calls"]):
+        xs = [R.draw_input(rng, n) for _ in range(rows)]
+        in_stride = max((n + 3) // 4 * 4, 4) + (0 if sh["in_stride16"] else 1)
+        host = np.zeros((rows, in_stride, 2), np.int16)
+        host[:, :n] = np.stack(xs)
+        xd = dev(host)[:, :n]
+        exps = [m.step(xs[r], flush) for r, (_, m) in enumerate(ps)]
+        n_out = len(exps[0])
+        out_stride = (n_out + _RS_GUARD + 3) // 4 * 4 + (0 if sh["out_stride16"] else 1)
+        out = torch.full((rows, out_stride, 2), _RS_GUARD_VALUE, dtype=torch.int16, device="cuda")
+        s0 = S.resample_stats()
+        S.resample_step_batched(ups, decs, xd, out, flush)
+        rose = tuple(b - c for c, b in zip(s0, S.resample_stats()))
+        if n_out == 0:
+            assert rose == (0, 0, 0, 0), (what, k, rose)
+        else:  # one launch per 64 rows where the dispatch rule says so, else the loop over the rows
+            assert rose == _one_hot(2 if R.bank_eligible(sh) else 3), (what, k, rose)
+        got = out.cpu().numpy()
+        assert (got[:, n_out:] == _RS_GUARD_VALUE).all(), (what, k)
+        for r, (g, m) in enumerate(ps):
+            assert got[r, :n_out].tobytes() == exps[r].tobytes(), (what, k, r)
+            m.same_decim_state(g.dec, (what, k, r))
+        for r in sorted({0, rows // 2, rows - 1}):  # the model's copy replays a history on the CPU: three rows
+            g, m = ps[r]
+            m.same_up_state(g.up, probe, (what, k, r))

@@ -33,11 +33,15 @@ DEC_TYPES = {0: ("complex<float>", "complex<float>", "complex<float>", "float"),
 FUSED, PAIR, BANK, LOOP = range(4)
 
 
-@pytest.fixture(scope="module", autouse=True)
-def fused_on_every_shape_it_takes(S):
+def force_fused(S):
     S.resample_set_min_tiles(1)
     yield
     S.resample_set_min_tiles(0)
+
+
+@pytest.fixture(scope="module", autouse=True)
+def fused_on_every_shape_it_takes(S):
+    yield from force_fused(S)
 
 
 def decim_taps(kind, M, ntaps):
@@ -86,20 +90,24 @@ def clamp_share(outs):
 _REF = {}
 
 
-def reference(O, kind, L, Nu, M, Nd, uvar=0, dvar=1, cu=None, cd=None, tag=None):
+def reference(O, kind, L, Nu, M, Nd, uvar=0, dvar=1, cu=None, cd=None, tag=None, ls=None):
     """x, calls, taps, the decimator's left shift and the oracle's output of
     every call; computed once per case.  "full": the left shift is the smallest
     for which at least 10 % of the oracle's outputs sit on +-32767 (the
     interpolator's clamp bites at any shift, the decimator's only then), and
-    that share is below 95 % -- asserted on the oracle alone."""
+    that share is below 95 % -- asserted on the oracle alone.  A caller that
+    passes its own taps (cu, cd) may pass the left shift too (ls): it is then
+    used as given; any kind but "full" takes the moderate input of "sinc"."""
     key = (kind, L, Nu, M, Nd, uvar, dvar, tag)
     if key not in _REF:
         cu = make_taps(kind, L, Nu) if cu is None else cu
         cd = decim_taps(kind, M, Nd) if cd is None else cd
         calls, total = shape_calls(L, Nu, M)
-        x = signal(O, kind, 0, total + 8)
-        ls, outs = 0, oracle_chain(O, x, calls, uvar, L, cu, dvar, M, cd, 0)
-        if kind == "full":
+        x = signal(O, "full" if kind == "full" else "sinc", 0, total + 8)
+        given = ls is not None
+        ls = ls if given else 0
+        outs = oracle_chain(O, x, calls, uvar, L, cu, dvar, M, cd, ls)
+        if kind == "full" and not given:
             while clamp_share(outs) < 0.10:
                 ls += 1
                 assert ls < 32, "no left shift puts 10 % of the outputs on the clamp"
@@ -129,10 +137,14 @@ def same_state(S, up, dec, tup, tdec, ls, probe, where):
     assert np.array_equal(ya.cpu().numpy(), yb.cpu().numpy()), where
 
 
-def run_and_check(S, ref, L, M, want, uvar=0, dvar=1, ioff=0, ooff=0):
+GUARD_VALUE = 0x5A5A
+
+
+def run_and_check(S, ref, L, M, want, uvar=0, dvar=1, ioff=0, ooff=0, guard=0):
     """Step the chain over the calls; after each: outputs, which counter rose
-    (want: index into resample_stats()), and both handles' state against twin
-    handles stepped through the two single operators."""
+    (want: index into resample_stats()), both handles' state against twin
+    handles stepped through the two single operators, and the samples around
+    the output (guard more behind it) keep their fill value."""
     import torch
     up, dec = handles(S, ref, L, M, uvar, dvar)
     tup, tdec = handles(S, ref, L, M, uvar, dvar)
@@ -142,11 +154,13 @@ def run_and_check(S, ref, L, M, want, uvar=0, dvar=1, ioff=0, ooff=0):
     for k, (off, n, last) in enumerate(ref["calls"]):
         xs = xd[ioff + off:ioff + off + n]
         want_y = ref["outs"][k]
-        y = torch.empty((len(want_y) + 4, 2), dtype=torch.int16, device="cuda")[ooff:ooff + len(want_y)]
+        buf = torch.full((len(want_y) + 4 + guard, 2), GUARD_VALUE, dtype=torch.int16, device="cuda")
+        y = buf[ooff:ooff + len(want_y)]
         s0 = S.resample_stats()
         rs.step(xs, y, last)
         s1 = S.resample_stats()
         assert np.array_equal(y.cpu().numpy(), want_y), k
+        assert (buf[:ooff] == GUARD_VALUE).all() and (buf[ooff + len(want_y):] == GUARD_VALUE).all(), k
         assert tuple(b - a for a, b in zip(s0, s1)) == tuple(int(i == want) for i in range(4)), k
         yt = tdec.step(tup.step(xs, None, last))
         assert np.array_equal(yt.cpu().numpy(), want_y), k
