@@ -5,8 +5,6 @@
 // parallel.
 #pragma once
 #include <algorithm>
-#include <map>
-#include <mutex>
 
 #include "ops.h"
 
@@ -26,23 +24,6 @@ constexpr int kCfBlock = 512, kCfGrid = 1024;
 // NT = 0: the tap count at run time (any N <= kCfMaxTaps), dynamic LDS.
 template <int M>
 constexpr int cf32_r() { return M == 1 ? 8 : (M <= 3 ? 4 : 16 / M); }
-
-// allow a kernel's dynamic LDS beyond the default limit (once per kernel and size)
-inline int raise_lds_limit(const void *kern, size_t bytes) {
-    static std::mutex mu;
-    static std::map<const void *, size_t> set;
-    std::lock_guard<std::mutex> g(mu);
-    size_t &cur = set[kern];
-    if (bytes > cur) {
-        hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) {  // not cached: the next call tries again
-            set_error(std::string("hipFuncSetAttribute(MaxDynamicSharedMemorySize): ") + hipGetErrorString(e));
-            return SRCDSP_ERR_HIP;
-        }
-        cur = bytes;
-    }
-    return SRCDSP_OK;
-}
 
 template <int NT, int M = 4>
 int launch_cf32(DecimLaunch L, int channels, bool fma, hipStream_t s) {

@@ -35,21 +35,10 @@ __global__ __launch_bounds__(kUpBlockD) void modulate_tile_dot2(const ModLaunch 
     extern __shared__ uint4 ug[];
     const UpmixLaunch &P = Q.up;
     const int c = blockIdx.y;
-    int16_t *tab = (int16_t *)((char *)ug + P.tab_off);
-    // visible to the epilogue through the tile's own barriers
-    const unsigned nv = P.N / 8;
-    for (unsigned i = threadIdx.x; i < nv; i += kUpBlockD) ((uint4 *)tab)[i] = ((const uint4 *)P.table)[i];
-    for (unsigned i = 8 * nv + threadIdx.x; i < P.N; i += kUpBlockD) tab[i] = P.table[i];
-    const uint32_t mw = P.mix[c];
     UpMixEpilogue epi;
-    epi.tab = tab;
-    epi.N = P.N;
-    epi.freq = mw >> 16;
-    epi.phi_tile = phase_at((unsigned long)LR * kUpRD * kUpBlockD * blockIdx.x, mw & 0xffffu, epi.freq, P.N);
-    const uint8_t *row = Q.bits + c * Q.bits_stride;
-    if (Q.kind == MAPPER_QPSK && blockIdx.x == 0 && threadIdx.x == 0 && Q.st_out[c])
-        *Q.st_out[c] = mapper_qpsk_state(row[Q.n_bits - 2], row[Q.n_bits - 1]);  // modulators.h:177, the last pair
-    const UpBitsIn src{Q.kind, row, Q.pk + c * Q.pk_stride};
+    upmix_stage_table(epi, P, ug);
+    upmix_aim<LR>(epi, P, c);
+    const UpBitsIn src = mod_bits_row(Q, c);
     up_dot2_tile<LR, true, 3, PPC>(src, P.n_in, P.n_total, P.hist_in[c], P.hist_out[c], P.pairs, P.H, P.shift,
                                    P.out + c * P.out_stride, epi);
 }
@@ -63,88 +52,20 @@ bool fused_takes(const srcdsp_up_state &u, const MixerState &m, const void *d_bi
 int fused_launch(const srcdsp_mapper_t *maps, const srcdsp_up_t *ups, const srcdsp_mixer_t *mixers, int nc,
                  const void *d_bits, size_t bits_stride, void *d_out, size_t out_stride, size_t n_bits, size_t n_sym,
                  long n_total, bool iter, hipStream_t s) {
-    srcdsp_up_state &u0 = ups[0]->u;
-    MapperState &lead = maps[0]->m;
+    const srcdsp_up_state &u0 = ups[0]->u;
     ModLaunch Q{};
-    UpmixLaunch &P = Q.up;
-    Q.kind = lead.kind;
-    Q.bits = (const uint8_t *)d_bits;
-    Q.bits_stride = (long)bits_stride;
-    Q.n_bits = (long)n_bits;
-    if (Q.kind == MAPPER_SDPSK && n_bits) {
-        const size_t rw = pk_row_words(n_bits);
-        int rc = lead.sym.reserve(4 * rw * (size_t)nc);
-        if (!rc) rc = mapper_launch(lead, maps, nc, d_bits, bits_stride, lead.sym.d, rw, n_bits, kMapperStates, s);
-        if (rc) return rc;
-        Q.pk = lead.sym.dev<uint32_t>();
-        Q.pk_stride = (long)rw;
-    }
-    P.out = (uint32_t *)d_out;
-    P.pairs = u0.d_pair;
-    P.table = mixers[0]->m.d_table;
-    P.n_in = (long)n_sym;
-    P.n_total = n_total;
-    P.out_stride = (long)out_stride;
-    P.H = u0.H;
-    P.shift = iter ? 0u : (unsigned)(15 - u0.left_shift_factor);
-    P.N = mixers[0]->m.N;
-    const size_t tile_lds = up_dot2_smem(u0.H, u0.L);
-    P.tab_off = (unsigned)tile_lds;
-    const size_t smem = tile_lds + ((2 * (size_t)P.N + 15) & ~(size_t)15);
-    const bool qpsk_state = Q.kind == MAPPER_QPSK && n_bits;
-    for (int c = 0; c < nc; ++c) {
-        MixerState &m = mixers[c]->m;
-        int rc = chan_begin(ups[c]->u, s, P.hist_in[c], P.hist_out[c]);
-        if (!rc) rc = m.order.before(s);
-        if (!rc && qpsk_state) {
-            MapperRowState row;
-            rc = mapper_begin(maps[c]->m, s, row);
-            Q.st_out[c] = row.out;
-        }
-        if (rc) return rc;
-        P.mix[c] = m.word();
-    }
-    constexpr int TI = kUpRD * kUpBlockD;
-    const int PP = (u0.H + 1) / 2;
-    const dim3 grid((unsigned)((n_total + TI - 1) / TI), (unsigned)nc);
-#define SRCDSP_MOD(LR, PPV) hipLaunchKernelGGL((modulate_tile_dot2<LR, PPV>), grid, dim3(kUpBlockD), smem, s, Q)
-    // the compile-time shapes of up_tile_dot2: 16, 32 or 64 taps per phase
-#define SRCDSP_MOD_PP(LR, PPV)        \
-    if (u0.L == LR && PP == PPV) {    \
-        SRCDSP_MOD(LR, PPV);          \
-    } else
-    SRCDSP_MOD_PP(2, 8)
-    SRCDSP_MOD_PP(2, 16)
-    SRCDSP_MOD_PP(2, 32)
-    SRCDSP_MOD_PP(4, 8)
-    SRCDSP_MOD_PP(4, 16)
-    SRCDSP_MOD_PP(4, 32)
-    SRCDSP_MOD_PP(8, 8)
-    SRCDSP_MOD_PP(8, 16)
-#undef SRCDSP_MOD_PP
-    switch (u0.L) {
-    case 2: SRCDSP_MOD(2, 0); break;
-    case 3: SRCDSP_MOD(3, 0); break;
-    case 4: SRCDSP_MOD(4, 0); break;
-    case 5: SRCDSP_MOD(5, 0); break;
-    case 6: SRCDSP_MOD(6, 0); break;
-    case 7: SRCDSP_MOD(7, 0); break;
-    default: SRCDSP_MOD(8, 0); break;
-    }
-#undef SRCDSP_MOD
-    SRCDSP_HIP_TRY(hipGetLastError());
-    const unsigned long n_out = (unsigned long)u0.L * (unsigned long)n_total;
-    for (int c = 0; c < nc; ++c) {
-        MixerState &m = mixers[c]->m;
-        m.advance(n_out);
-        int rc = chan_commit(ups[c]->u, s);
-        if (!rc) rc = m.order.after(s);
-        // SDPSK: the tile read the mapper's packed states, so the mapper's
-        // next step (which may rewrite them) is ordered after the tile too
-        if (!rc && n_bits) rc = qpsk_state ? mapper_commit(maps[c]->m, s) : maps[c]->m.order.after(s);
-        if (rc) return rc;
-    }
-    return SRCDSP_OK;
+    size_t smem = 0;
+    int rc = mod_launch_begin(Q, maps, ups, mixers, nc, d_bits, bits_stride, d_out, out_stride, n_bits, n_sym, n_total,
+                              iter, s, &smem, upmix_no_more);
+    if (rc) return rc;
+    const dim3 grid((unsigned)up_tiles(n_total), (unsigned)nc);
+    const bool served = up_dot2_dispatch<UpDot2Standard>(u0.L, (u0.H + 1) / 2, [&](auto lr, auto ppc) {
+        hipLaunchKernelGGL((modulate_tile_dot2<decltype(lr)::value, decltype(ppc)::value>), grid, dim3(kUpBlockD), smem,
+                           s, Q);
+    });
+    rc = up_dot2_launched(served);
+    if (rc) return rc;
+    return mod_launch_commit(maps, ups, mixers, nc, n_bits, n_total, s, upmix_no_more);
 }
 
 // one checked chain of n_out > 0; *fused tells which path served it

@@ -33,21 +33,10 @@ __global__ __launch_bounds__(kUpBlockD) void modoffset_tile_dot2(const ModOffLau
     const ModLaunch &Q = A.mod;
     const UpmixLaunch &P = Q.up;
     const int c = blockIdx.y;
-    int16_t *tab = (int16_t *)((char *)ug + P.tab_off);
-    // visible to the epilogue through the tile's own barriers
-    const unsigned nv = P.N / 8;
-    for (unsigned i = threadIdx.x; i < nv; i += kUpBlockD) ((uint4 *)tab)[i] = ((const uint4 *)P.table)[i];
-    for (unsigned i = 8 * nv + threadIdx.x; i < P.N; i += kUpBlockD) tab[i] = P.table[i];
-    const uint32_t mw = P.mix[c];
     UpMixEpilogue epi;
-    epi.tab = tab;
-    epi.N = P.N;
-    epi.freq = mw >> 16;
-    epi.phi_tile = phase_at((unsigned long)LR * kUpRD * kUpBlockD * blockIdx.x, mw & 0xffffu, epi.freq, P.N);
-    const uint8_t *row = Q.bits + c * Q.bits_stride;
-    if (Q.kind == MAPPER_QPSK && blockIdx.x == 0 && threadIdx.x == 0 && Q.st_out[c])
-        *Q.st_out[c] = mapper_qpsk_state(row[Q.n_bits - 2], row[Q.n_bits - 1]);  // modulators.h:177, the last pair
-    const UpBitsIn src{Q.kind, row, Q.pk + c * Q.pk_stride};
+    upmix_stage_table(epi, P, ug);
+    upmix_aim<LR>(epi, P, c);
+    const UpBitsIn src = mod_bits_row(Q, c);
     const UpQStagger stg{A.D, A.carry_in[c], A.carry_out[c], (uint16_t *)((char *)ug + A.slot_off)};
     up_dot2_tile<LR, true, 3, PPC>(src, P.n_in, P.n_total, P.hist_in[c], P.hist_out[c], P.pairs, P.H, P.shift,
                                    P.out + c * P.out_stride, epi, stg);
@@ -63,41 +52,19 @@ bool fused_takes(const srcdsp_up_state &u, const MixerState &m, const StaggerSta
 int fused_launch(const srcdsp_mapper_t *maps, const srcdsp_up_t *ups, const srcdsp_stagger_t *stags,
                  const srcdsp_mixer_t *mixers, int nc, const void *d_bits, size_t bits_stride, void *d_out,
                  size_t out_stride, size_t n_bits, size_t n_sym, long n_total, bool iter, hipStream_t s) {
-    srcdsp_up_state &u0 = ups[0]->u;
+    const srcdsp_up_state &u0 = ups[0]->u;
     ModOffLaunch A{};
     size_t smem = 0;
     int rc = modoff_launch_begin(A, maps, ups, stags, mixers, nc, d_bits, bits_stride, d_out, out_stride, n_bits, n_sym,
                                  n_total, iter, s, &smem);
     if (rc) return rc;
-    constexpr int TI = kUpRD * kUpBlockD;
-    const int PP = (u0.H + 1) / 2;
-    const dim3 grid((unsigned)((n_total + TI - 1) / TI), (unsigned)nc);
-#define SRCDSP_MODOFF(LR, PPV) hipLaunchKernelGGL((modoffset_tile_dot2<LR, PPV>), grid, dim3(kUpBlockD), smem, s, A)
-    // the compile-time shapes of up_tile_dot2: 16, 32 or 64 taps per phase
-#define SRCDSP_MODOFF_PP(LR, PPV)     \
-    if (u0.L == LR && PP == PPV) {    \
-        SRCDSP_MODOFF(LR, PPV);       \
-    } else
-    SRCDSP_MODOFF_PP(2, 8)
-    SRCDSP_MODOFF_PP(2, 16)
-    SRCDSP_MODOFF_PP(2, 32)
-    SRCDSP_MODOFF_PP(4, 8)
-    SRCDSP_MODOFF_PP(4, 16)
-    SRCDSP_MODOFF_PP(4, 32)
-    SRCDSP_MODOFF_PP(8, 8)
-    SRCDSP_MODOFF_PP(8, 16)
-#undef SRCDSP_MODOFF_PP
-    switch (u0.L) {
-    case 2: SRCDSP_MODOFF(2, 0); break;
-    case 3: SRCDSP_MODOFF(3, 0); break;
-    case 4: SRCDSP_MODOFF(4, 0); break;
-    case 5: SRCDSP_MODOFF(5, 0); break;
-    case 6: SRCDSP_MODOFF(6, 0); break;
-    case 7: SRCDSP_MODOFF(7, 0); break;
-    default: SRCDSP_MODOFF(8, 0); break;
-    }
-#undef SRCDSP_MODOFF
-    SRCDSP_HIP_TRY(hipGetLastError());
+    const dim3 grid((unsigned)up_tiles(n_total), (unsigned)nc);
+    const bool served = up_dot2_dispatch<UpDot2Standard>(u0.L, (u0.H + 1) / 2, [&](auto lr, auto ppc) {
+        hipLaunchKernelGGL((modoffset_tile_dot2<decltype(lr)::value, decltype(ppc)::value>), grid, dim3(kUpBlockD), smem,
+                           s, A);
+    });
+    rc = up_dot2_launched(served);
+    if (rc) return rc;
     return modoff_launch_commit(maps, ups, stags, mixers, nc, n_bits, n_total, s);
 }
 

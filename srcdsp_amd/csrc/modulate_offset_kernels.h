@@ -1,8 +1,10 @@
 // modulate_offset_kernels.h -- what the offset modulator bank
 // (modulate_offset.hip) and the summing modulator bank (modulate_sum.hip)
 // share: the tile's stagger policy, the launch description, the size and
-// sharing rules of a bank call, and the two halves of a bank launch on either
-// side of the kernel (every handle's begin, every handle's commit).
+// sharing rules of a bank call, and the stagger layer of the two halves of a
+// bank launch on either side of the kernel (every handle's begin, every
+// handle's commit; the layers below are in modulate_kernels.h and
+// upmix_kernels.h).
 #pragma once
 #include <string>
 
@@ -32,7 +34,7 @@ struct UpQStaggerOf {
         const int o = LR - D + t;
         slot[8 - D + t] = j0 == 0 ? (uint16_t)carry_in[t] : (uint16_t)tile_q(halo - 1, o);
         const long jl = n_total - 1 - j0;
-        if (jl < kUpRD * kUpBlockD) carry_out[t] = (int16_t)(uint16_t)tile_q(halo + (int)jl, o);
+        if (jl < kUpTile) carry_out[t] = (int16_t)(uint16_t)tile_q(halo + (int)jl, o);
     }
     __device__ __forceinline__ uint4 seeds() const { return *(const uint4 *)slot; }
 };
@@ -74,79 +76,30 @@ inline int modulate_bank_check(const srcdsp_mapper_t *mappers, const srcdsp_up_t
     return SRCDSP_OK;
 }
 
-// The part of a bank launch ahead of the kernel, for nc <= kMaxBatch chains of
-// a shape the tile takes: the SDPSK mapper's launches, the launch description
-// and every handle's begin.  *smem: the dynamic LDS of the launch.  stags ==
-// nullptr: no stagger (A.D = 0, no carry).
+// The stagger layer of a bank launch's two halves, on mod_launch_begin /
+// mod_launch_commit (modulate_kernels.h), for nc <= kMaxBatch chains of a shape
+// the tile takes.  Ahead of the kernel: the layers below with every stagger's
+// begin, and the seed slot behind the mixer's table.  *smem: the dynamic LDS of
+// the launch.  stags == nullptr: no stagger (A.D = 0, no carry).
 inline int modoff_launch_begin(ModOffLaunch &A, const srcdsp_mapper_t *maps, const srcdsp_up_t *ups,
                                const srcdsp_stagger_t *stags, const srcdsp_mixer_t *mixers, int nc, const void *d_bits,
                                size_t bits_stride, void *d_out, size_t out_stride, size_t n_bits, size_t n_sym,
                                long n_total, bool iter, hipStream_t s, size_t *smem) {
-    srcdsp_up_state &u0 = ups[0]->u;
-    MapperState &lead = maps[0]->m;
-    ModLaunch &Q = A.mod;
-    UpmixLaunch &P = Q.up;
     A.D = stags ? (int)stags[0]->g.D : 0;
-    Q.kind = lead.kind;
-    Q.bits = (const uint8_t *)d_bits;
-    Q.bits_stride = (long)bits_stride;
-    Q.n_bits = (long)n_bits;
-    if (Q.kind == MAPPER_SDPSK && n_bits) {
-        const size_t rw = pk_row_words(n_bits);
-        int rc = lead.sym.reserve(4 * rw * (size_t)nc);
-        if (!rc) rc = mapper_launch(lead, maps, nc, d_bits, bits_stride, lead.sym.d, rw, n_bits, kMapperStates, s);
-        if (rc) return rc;
-        Q.pk = lead.sym.dev<uint32_t>();
-        Q.pk_stride = (long)rw;
-    }
-    P.out = (uint32_t *)d_out;
-    P.pairs = u0.d_pair;
-    P.table = mixers[0]->m.d_table;
-    P.n_in = (long)n_sym;
-    P.n_total = n_total;
-    P.out_stride = (long)out_stride;
-    P.H = u0.H;
-    P.shift = iter ? 0u : (unsigned)(15 - u0.left_shift_factor);
-    P.N = mixers[0]->m.N;
-    const size_t tile_lds = up_dot2_smem(u0.H, u0.L);
-    P.tab_off = (unsigned)tile_lds;
-    A.slot_off = (unsigned)(tile_lds + ((2 * (size_t)P.N + 15) & ~(size_t)15));
+    int rc = mod_launch_begin(A.mod, maps, ups, mixers, nc, d_bits, bits_stride, d_out, out_stride, n_bits, n_sym,
+                              n_total, iter, s, smem, [&](int c) {
+                                  return stags ? stagger_begin(stags[c]->g, s, A.carry_in[c], A.carry_out[c]) : SRCDSP_OK;
+                              });
+    A.slot_off = (unsigned)*smem;
     *smem = A.slot_off + 16;
-    const bool qpsk_state = Q.kind == MAPPER_QPSK && n_bits;
-    for (int c = 0; c < nc; ++c) {
-        MixerState &m = mixers[c]->m;
-        int rc = chan_begin(ups[c]->u, s, P.hist_in[c], P.hist_out[c]);
-        if (!rc) rc = m.order.before(s);
-        if (!rc && stags) rc = stagger_begin(stags[c]->g, s, A.carry_in[c], A.carry_out[c]);
-        if (!rc && qpsk_state) {
-            MapperRowState row;
-            rc = mapper_begin(maps[c]->m, s, row);
-            Q.st_out[c] = row.out;
-        }
-        if (rc) return rc;
-        P.mix[c] = m.word();
-    }
-    return SRCDSP_OK;
+    return rc;
 }
 
-// The part behind the kernel: every mixer advanced by the row's samples and
-// every handle's commit
+// Behind the kernel: the layers below with every stagger's commit
 inline int modoff_launch_commit(const srcdsp_mapper_t *maps, const srcdsp_up_t *ups, const srcdsp_stagger_t *stags,
                                 const srcdsp_mixer_t *mixers, int nc, size_t n_bits, long n_total, hipStream_t s) {
-    const bool qpsk_state = maps[0]->m.kind == MAPPER_QPSK && n_bits;
-    const unsigned long n_out = (unsigned long)ups[0]->u.L * (unsigned long)n_total;
-    for (int c = 0; c < nc; ++c) {
-        MixerState &m = mixers[c]->m;
-        m.advance(n_out);
-        int rc = chan_commit(ups[c]->u, s);
-        if (!rc) rc = m.order.after(s);
-        if (!rc && stags) rc = stagger_commit(stags[c]->g, s);
-        // SDPSK: the tile read the mapper's packed states, so the mapper's
-        // next step (which may rewrite them) is ordered after the tile too
-        if (!rc && n_bits) rc = qpsk_state ? mapper_commit(maps[c]->m, s) : maps[c]->m.order.after(s);
-        if (rc) return rc;
-    }
-    return SRCDSP_OK;
+    return mod_launch_commit(maps, ups, mixers, nc, n_bits, n_total, s,
+                             [&](int c) { return stags ? stagger_commit(stags[c]->g, s) : SRCDSP_OK; });
 }
 
 }  // namespace srcdsp

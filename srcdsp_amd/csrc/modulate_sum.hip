@@ -38,8 +38,8 @@ namespace srcdsp {
 namespace {
 PathCounter g_fused_calls, g_bank_calls;
 
-constexpr int kSumTile = kUpRD * kUpBlockD;  // symbols per workgroup
-bool modsum_serves(unsigned L) { return L == 2 || L == 4 || L == 8; }  // the kernel's L; the others go to the bank
+// the kernel's L (a workgroup takes kUpTile symbols); the others go to the bank
+bool modsum_serves(unsigned L) { return UpDot2SummingTile::has((int)L, 0); }
 
 // The calls the fused kernel serves of those it takes: at least min_tiles tiles
 // (0: none) and at most max_channels chains.  Measured (DESIGN 5.8c,
@@ -132,27 +132,16 @@ __global__ __launch_bounds__(kUpBlockD) void modsum_tile_dot2(const ModOffLaunch
     const ModLaunch &Q = A.mod;
     const UpmixLaunch &P = Q.up;
     const int t = threadIdx.x;
-    int16_t *tab = (int16_t *)((char *)ug + P.tab_off);
-    // once per workgroup; visible to the epilogue through the tile's own barriers
-    const unsigned nv = P.N / 8;
-    for (unsigned i = t; i < nv; i += kUpBlockD) ((uint4 *)tab)[i] = ((const uint4 *)P.table)[i];
-    for (unsigned i = 8 * nv + t; i < P.N; i += kUpBlockD) tab[i] = P.table[i];
     typedef typename std::conditional<LDSS, UpMixSumLds<NW>, UpMixSumRegs<NW>>::type Sum;
     Sum epi;
-    epi.mix.tab = tab;
-    epi.mix.N = P.N;
+    upmix_stage_table(epi.mix, P, ug);  // once per workgroup
     epi.zero((char *)ug + A.slot_off + 16);
-    const unsigned long w0 = (unsigned long)LR * kSumTile * blockIdx.x;  // the tile's first output word
+    const unsigned long w0 = upmix_tile_word<LR>();
     for (int c = 0; c < nc; ++c) {
         // the chain before is done with the planes' padding granules and the seed slot
         if (c) __syncthreads();
-        const uint32_t mw = P.mix[c];
-        epi.mix.freq = mw >> 16;
-        epi.mix.phi_tile = phase_at(w0, mw & 0xffffu, epi.mix.freq, P.N);
-        const uint8_t *row = Q.bits + c * Q.bits_stride;
-        if (Q.kind == MAPPER_QPSK && blockIdx.x == 0 && t == 0 && Q.st_out[c])
-            *Q.st_out[c] = mapper_qpsk_state(row[Q.n_bits - 2], row[Q.n_bits - 1]);  // modulators.h:177, the last pair
-        const UpBitsIn src{Q.kind, row, Q.pk + c * Q.pk_stride};
+        upmix_aim<LR>(epi.mix, P, c, w0);
+        const UpBitsIn src = mod_bits_row(Q, c);
         if constexpr (STG && LR == 8) {
             // the delay of half a symbol, compiled in: eight emit loops for a
             // run-time delay, each over 128 sums, do not fit the register file
@@ -175,7 +164,7 @@ __global__ __launch_bounds__(kUpBlockD) void modsum_tile_dot2(const ModOffLaunch
         ug[t * STR + k] = make_uint4(epi.word(4 * k, cshift), epi.word(4 * k + 1, cshift), epi.word(4 * k + 2, cshift),
                                      epi.word(4 * k + 3, cshift));
     __syncthreads();
-    up_tile_flush<LR, true>(ug, t, wire, (long)kSumTile * blockIdx.x, P.n_total);
+    up_tile_flush<LR, true>(ug, t, wire, (long)kUpTile * blockIdx.x, P.n_total);
 }
 
 // what the fused kernel takes of a checked call, the tile count aside
@@ -193,39 +182,13 @@ int launch_one(const ModOffLaunch &A, int nc, unsigned shift, void *d_out, unsig
     auto kern = modsum_tile_dot2<LR, PPC, STG, LDSS>;
     if (LDSS) {
         smem += modsum_lds_bytes(LR);
-        static std::atomic<bool> raised{false};  // beyond the default limit of dynamic LDS: once per kernel
-        if (!raised.load(std::memory_order_acquire)) {
-            SRCDSP_HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)(up_dot2_smem(kUpMaxTaps / LR, LR) + 2 * kUpmixMaxN + 32 +
-                                                     modsum_lds_bytes(LR))));
-            raised.store(true, std::memory_order_release);
-        }
+        // beyond the default limit of dynamic LDS: the kernel's largest launch, so once per kernel
+        int rc = raise_lds_limit((const void *)kern, up_dot2_smem(kUpMaxTaps / LR, LR) + 2 * kUpmixMaxN + 32 +
+                                                         modsum_lds_bytes(LR));
+        if (rc) return rc;
     }
     hipLaunchKernelGGL(kern, dim3(tiles), dim3(kUpBlockD), smem, s, A, nc, shift, (uint32_t *)d_out);
-    SRCDSP_HIP_TRY(hipGetLastError());
     return SRCDSP_OK;
-}
-
-template <int LR, bool STG>
-int launch_pp(const ModOffLaunch &A, int PP, int nc, unsigned shift, void *d_out, unsigned tiles, size_t smem,
-              hipStream_t s) {
-    // the compile-time shapes of up_tile_dot2: 16, 32 or 64 taps per phase.  L = 8
-    // has 16 only: modsum_tile_dot2<8, 16, *> gave a wrong wire on hardware
-    // (tests/test_gpu_modulate_sum_sweep.py at 31 and 32 taps per phase, with and
-    // without staggers; the same with its first pair through the builtin, so not
-    // the inline v_dot2), where every other instantiation and the run-time kernel
-    // on the same shapes equal the model, so these run the run-time kernel
-    switch (PP) {
-    case 8: return launch_one<LR, 8, STG>(A, nc, shift, d_out, tiles, smem, s);
-    case 16:
-        if constexpr (LR < 8) return launch_one<LR, 16, STG>(A, nc, shift, d_out, tiles, smem, s);
-        break;
-    case 32:
-        if constexpr (LR < 8) return launch_one<LR, 32, STG>(A, nc, shift, d_out, tiles, smem, s);
-        break;
-    default: break;
-    }
-    return launch_one<LR, 0, STG>(A, nc, shift, d_out, tiles, smem, s);
 }
 
 // the checked call on the fused kernel: a shape fused_takes accepts
@@ -238,17 +201,13 @@ int sum_fused(const srcdsp_mapper_t *maps, const srcdsp_up_t *ups, const srcdsp_
     int rc = modoff_launch_begin(A, maps, ups, stags, mixers, nc, d_bits, bits_stride, nullptr, 0, n_bits, n_sym,
                                  n_total, false, s, &smem);
     if (rc) return rc;
-    const unsigned tiles = (unsigned)((n_total + kSumTile - 1) / kSumTile);
-    const int PP = (u0.H + 1) / 2;
-    if (u0.L == 2)
-        rc = stags ? launch_pp<2, true>(A, PP, nc, shift, d_out, tiles, smem, s)
-                   : launch_pp<2, false>(A, PP, nc, shift, d_out, tiles, smem, s);
-    else if (u0.L == 4)
-        rc = stags ? launch_pp<4, true>(A, PP, nc, shift, d_out, tiles, smem, s)
-                   : launch_pp<4, false>(A, PP, nc, shift, d_out, tiles, smem, s);
-    else
-        rc = stags ? launch_pp<8, true>(A, PP, nc, shift, d_out, tiles, smem, s)
-                   : launch_pp<8, false>(A, PP, nc, shift, d_out, tiles, smem, s);
+    const unsigned tiles = (unsigned)up_tiles(n_total);
+    const bool served = up_dot2_dispatch<UpDot2SummingTile>(u0.L, (u0.H + 1) / 2, [&](auto lr, auto ppc) {
+        constexpr int LR = decltype(lr)::value, PPC = decltype(ppc)::value;
+        rc = stags ? launch_one<LR, PPC, true>(A, nc, shift, d_out, tiles, smem, s)
+                   : launch_one<LR, PPC, false>(A, nc, shift, d_out, tiles, smem, s);
+    });
+    if (!rc) rc = up_dot2_launched(served);
     if (rc) return rc;
     return modoff_launch_commit(maps, ups, stags, mixers, nc, n_bits, n_total, s);
 }
@@ -303,7 +262,7 @@ SRCDSP_API int srcdsp_modulate_sum_step(const srcdsp_mapper_t *mappers, const sr
     const long n_total = (long)(n_out / u0.L);
     const SumRoute route = modsum_route(u0.L);
     if (fused_takes(u0, mixers[0]->m, staggers, channels, d_bits, bits_stride, d_out) && route.min_tiles > 0 &&
-        (n_total + kSumTile - 1) / kSumTile >= route.min_tiles && channels <= route.max_channels) {
+        up_tiles(n_total) >= route.min_tiles && channels <= route.max_channels) {
         rc = sum_fused(mappers, ups, staggers, mixers, channels, d_bits, bits_stride, d_out, n_bits, n_sym, n_total,
                        shift, (hipStream_t)stream);
         if (rc == SRCDSP_OK) g_fused_calls.hit();
@@ -323,7 +282,7 @@ SRCDSP_API int srcdsp_modulate_sum_stats(unsigned long *fused_calls, unsigned lo
 
 SRCDSP_API int srcdsp_modulate_sum_geometry(unsigned L, int *tile_symbols, long *min_tiles, int *max_channels) {
     const SumRoute route = modsum_route(L);
-    if (tile_symbols) *tile_symbols = kSumTile;
+    if (tile_symbols) *tile_symbols = kUpTile;
     if (min_tiles) *min_tiles = route.min_tiles;
     if (max_channels) *max_channels = route.max_channels;
     return SRCDSP_OK;

@@ -1,8 +1,28 @@
-// ops.h -- handle layouts shared between the operator translation units.
+// ops.h -- handle layouts shared between the operator translation units, and
+// the one cache of the kernels' raised dynamic-LDS limits.
 #pragma once
+#include <map>
+
 #include "common.h"
 
 namespace srcdsp {
+
+// allow a kernel's dynamic LDS beyond the default limit (once per kernel and size)
+inline int raise_lds_limit(const void *kern, size_t bytes) {
+    static std::mutex mu;
+    static std::map<const void *, size_t> set;
+    std::lock_guard<std::mutex> g(mu);
+    size_t &cur = set[kern];
+    if (bytes > cur) {
+        hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        if (e != hipSuccess) {  // not cached: the next call tries again
+            set_error(std::string("hipFuncSetAttribute(MaxDynamicSharedMemorySize): ") + hipGetErrorString(e));
+            return SRCDSP_ERR_HIP;
+        }
+        cur = bytes;
+    }
+    return SRCDSP_OK;
+}
 
 // Kernel-level sample/coefficient combinations.  Decimator variants 0-3 map
 // 1:1; FilterFir variant 1 (float in, float taps, complex<float> out with a

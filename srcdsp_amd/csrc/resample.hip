@@ -64,21 +64,7 @@ bool fused_serves(const srcdsp_up_state &u, const FirCore &f, const void *d_in, 
                   int channels) {
     if (!fused_takes(u, f, d_in, d_out)) return false;
     const long min_tiles = rs_route(u.L, f.M);
-    return min_tiles > 0 && (n_total + kRsTile - 1) / kRsTile * channels >= min_tiles;
-}
-
-template <int LR, int PPC>
-int launch_one(const ResampleLaunch &P, dim3 grid, size_t smem, hipStream_t s) {
-    auto kern = resample_tile_dot2<LR, PPC>;
-    static std::atomic<bool> raised{false};  // beyond the default limit of dynamic LDS: once per kernel
-    if (!raised.load(std::memory_order_acquire)) {
-        SRCDSP_HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)rs_smem(kUpMaxTaps / LR, LR, kRsMaxDecimTaps)));
-        raised.store(true, std::memory_order_release);
-    }
-    hipLaunchKernelGGL(kern, grid, dim3(kUpBlockD), smem, s, P);
-    SRCDSP_HIP_TRY(hipGetLastError());
-    return SRCDSP_OK;
+    return min_tiles > 0 && up_tiles(n_total) * channels >= min_tiles;
 }
 
 // nc <= kMaxBatch chains in one launch; the shape is one fused_takes accepts
@@ -111,23 +97,16 @@ int fused_launch(const srcdsp_up_t *ups, const srcdsp_decim_t *decims, int nc, c
         if (!rc) rc = chan_begin(decims[c]->core, s, P.dhist_in[c], P.dhist_out[c]);
         if (rc) return rc;
     }
-    const dim3 grid((unsigned)((n_total + kRsTile - 1) / kRsTile), (unsigned)nc);
-    int rc;
-    // the pairs per phase compiled in at the measured shapes (128 taps at L = 4
-    // and 8, 64 at L = 2); run-time taps for the rest
-    if (u0.L == 2 && PP == 16) rc = launch_one<2, 16>(P, grid, smem, s);
-    else if (u0.L == 4 && PP == 16) rc = launch_one<4, 16>(P, grid, smem, s);
-    else if (u0.L == 8 && PP == 8) rc = launch_one<8, 8>(P, grid, smem, s);
-    else
-        switch (u0.L) {
-        case 2: rc = launch_one<2, 0>(P, grid, smem, s); break;
-        case 3: rc = launch_one<3, 0>(P, grid, smem, s); break;
-        case 4: rc = launch_one<4, 0>(P, grid, smem, s); break;
-        case 5: rc = launch_one<5, 0>(P, grid, smem, s); break;
-        case 6: rc = launch_one<6, 0>(P, grid, smem, s); break;
-        case 7: rc = launch_one<7, 0>(P, grid, smem, s); break;
-        default: rc = launch_one<8, 0>(P, grid, smem, s); break;
-        }
+    const dim3 grid((unsigned)up_tiles(n_total), (unsigned)nc);
+    int rc = SRCDSP_OK;
+    const bool served = up_dot2_dispatch<UpDot2Resampler>(u0.L, PP, [&](auto lr, auto ppc) {
+        constexpr int LR = decltype(lr)::value;
+        auto kern = resample_tile_dot2<LR, decltype(ppc)::value>;
+        // beyond the default limit of dynamic LDS: the kernel's largest launch, so once per kernel
+        rc = raise_lds_limit((const void *)kern, rs_smem(kUpMaxTaps / LR, LR, kRsMaxDecimTaps));
+        if (!rc) hipLaunchKernelGGL(kern, grid, dim3(kUpBlockD), smem, s, P);
+    });
+    if (!rc) rc = up_dot2_launched(served);
     if (rc) return rc;
     for (int c = 0; c < nc; ++c) {
         rc = chan_commit(ups[c]->u, s);

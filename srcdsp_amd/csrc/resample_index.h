@@ -23,7 +23,7 @@
 
 namespace srcdsp {
 
-constexpr int kRsTile = 2048;  // inputs per tile: kUpRD * kUpBlockD of up_dot2_kernels.h
+constexpr int kRsTile = 2048;  // inputs per tile: kUpTile of up_dot2_kernels.h
 
 // halo words staged ahead of a tile's mid words: the N_d - 1 words the first
 // output's taps reach back, the word one deeper that the zero tap c[N_d] of

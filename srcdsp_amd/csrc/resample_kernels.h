@@ -48,7 +48,7 @@
 namespace srcdsp {
 
 constexpr int kRsMaxDecimTaps = 1024;
-static_assert(kRsTile == kUpRD * kUpBlockD, "the interpolator's tile");
+static_assert(kRsTile == kUpTile, "the interpolator's tile");
 static_assert(rs_smem(kUpMaxTaps / 8, 8, kRsMaxDecimTaps) <= 160 * 1024, "LDS of a CU");
 
 struct ResampleLaunch {

@@ -5,10 +5,20 @@
 // from bits, modulate_offset.hip adds the OQPSK stagger ahead of the mixer,
 // modulate_sum.hip runs it once per chain without its store phase and
 // resample.hip puts the decimator behind it in place of that phase.
+//
+// What the six have in common around the tile lives in one place each: which
+// instantiations <LR, PPC> a family has and which one a call runs in
+// up_dot2_dispatch.h; the tile's size, tile count and LDS here (kUpTile,
+// up_tiles, up_dot2_smem); the mixer's kernel prologue and the interpolator +
+// mixer half of a launch in upmix_kernels.h; the bits source's prologue and the
+// mapper's half in modulate_kernels.h; the stagger's in
+// modulate_offset_kernels.h.
 #pragma once
 #include <string>
 
 #include "ops.h"
+
+#include "up_dot2_dispatch.h"
 
 namespace srcdsp {
 
@@ -63,12 +73,27 @@ constexpr int kUpMaxTaps = 4096;
 // pairing needed H/2 + 1).  int16 x int16 -> int32 products, wrap-around
 // accumulate: exactly the reference's complex<int32_t> arithmetic.
 constexpr int kUpRD = 8, kUpBlockD = 256;
+constexpr int kUpTile = kUpRD * kUpBlockD;  // inputs per tile (workgroup)
+
+// tiles (grid.x) of a call of n_total inputs
+inline long up_tiles(long n_total) { return (n_total + kUpTile - 1) / kUpTile; }
 
 // dynamic LDS of one tile: the four input planes, reused for the staged output
 inline size_t up_dot2_smem(int H, unsigned L) {
-    const int PP = (H + 1) / 2, HG = (PP + 3) / 4, PGR = kUpRD * kUpBlockD / 8 + HG;
+    const int PP = (H + 1) / 2, HG = (PP + 3) / 4, PGR = kUpTile / 8 + HG;
     const size_t out_lds = 16 * (size_t)kUpBlockD * (kUpRD * L / 4 + 1);  // staged output tile
     return 4 * 16 * (size_t)PGR > out_lds ? 4 * 16 * (size_t)PGR : out_lds;
+}
+
+// behind up_dot2_dispatch (up_dot2_dispatch.h) and the launch in its callback:
+// a ratio the family has no kernel for is an error, as is a failed launch
+inline int up_dot2_launched(bool served) {
+    if (!served) {
+        set_error("v_dot2 tile: no kernel of this family for the interpolator's L");
+        return SRCDSP_ERR_UNSUPPORTED;
+    }
+    SRCDSP_HIP_TRY(hipGetLastError());
+    return SRCDSP_OK;
 }
 
 // Where a tile's input words come from (the staging policy SRC of

@@ -35,17 +35,9 @@ template <int LR, int PPC>
 __global__ __launch_bounds__(kUpBlockD) void upmix_tile_dot2(const UpmixLaunch P) {
     extern __shared__ uint4 ug[];
     const int c = blockIdx.y;
-    int16_t *tab = (int16_t *)((char *)ug + P.tab_off);
-    // visible to the epilogue through the tile's own barriers
-    const unsigned nv = P.N / 8;
-    for (unsigned i = threadIdx.x; i < nv; i += kUpBlockD) ((uint4 *)tab)[i] = ((const uint4 *)P.table)[i];
-    for (unsigned i = 8 * nv + threadIdx.x; i < P.N; i += kUpBlockD) tab[i] = P.table[i];
-    const uint32_t mw = P.mix[c];
     UpMixEpilogue epi;
-    epi.tab = tab;
-    epi.N = P.N;
-    epi.freq = mw >> 16;
-    epi.phi_tile = phase_at((unsigned long)LR * kUpRD * kUpBlockD * blockIdx.x, mw & 0xffffu, epi.freq, P.N);
+    upmix_stage_table(epi, P, ug);
+    upmix_aim<LR>(epi, P, c);
     up_dot2_tile<LR, true, 3, PPC>(UpWordsIn{P.in + c * P.in_stride}, P.n_in, P.n_total, P.hist_in[c], P.hist_out[c],
                                    P.pairs, P.H, P.shift, P.out + c * P.out_stride, epi);
 }
@@ -53,67 +45,21 @@ __global__ __launch_bounds__(kUpBlockD) void upmix_tile_dot2(const UpmixLaunch P
 // nc <= kMaxBatch chains in one launch; the shape is one upmix_fused_takes accepts
 int fused_launch(const srcdsp_up_t *ups, const srcdsp_mixer_t *mixers, int nc, const void *d_in, size_t in_stride,
                  void *d_out, size_t out_stride, size_t n_in, long n_total, bool iter, hipStream_t s) {
-    srcdsp_up_state &u0 = ups[0]->u;
+    const srcdsp_up_state &u0 = ups[0]->u;
     UpmixLaunch P{};
     P.in = (const uint32_t *)d_in;
-    P.out = (uint32_t *)d_out;
-    P.pairs = u0.d_pair;
-    P.table = mixers[0]->m.d_table;
-    P.n_in = (long)n_in;
-    P.n_total = n_total;
     P.in_stride = (long)in_stride;
-    P.out_stride = (long)out_stride;
-    P.H = u0.H;
-    P.shift = iter ? 0u : (unsigned)(15 - u0.left_shift_factor);
-    P.N = mixers[0]->m.N;
-    const size_t tile_lds = up_dot2_smem(u0.H, u0.L);
-    P.tab_off = (unsigned)tile_lds;
-    const size_t smem = tile_lds + ((2 * (size_t)P.N + 15) & ~(size_t)15);
-    for (int c = 0; c < nc; ++c) {
-        MixerState &m = mixers[c]->m;
-        int rc = chan_begin(ups[c]->u, s, P.hist_in[c], P.hist_out[c]);
-        if (!rc) rc = m.order.before(s);
-        if (rc) return rc;
-        P.mix[c] = m.word();
-    }
-    constexpr int TI = kUpRD * kUpBlockD;
-    const int PP = (u0.H + 1) / 2;
-    const dim3 grid((unsigned)((n_total + TI - 1) / TI), (unsigned)nc);
-#define SRCDSP_UPMIX(LR, PPV) hipLaunchKernelGGL((upmix_tile_dot2<LR, PPV>), grid, dim3(kUpBlockD), smem, s, P)
-    // the compile-time shapes of up_tile_dot2: 16, 32 or 64 taps per phase
-#define SRCDSP_UPMIX_PP(LR, PPV)      \
-    if (u0.L == LR && PP == PPV) {    \
-        SRCDSP_UPMIX(LR, PPV);        \
-    } else
-    SRCDSP_UPMIX_PP(2, 8)
-    SRCDSP_UPMIX_PP(2, 16)
-    SRCDSP_UPMIX_PP(2, 32)
-    SRCDSP_UPMIX_PP(4, 8)
-    SRCDSP_UPMIX_PP(4, 16)
-    SRCDSP_UPMIX_PP(4, 32)
-    SRCDSP_UPMIX_PP(8, 8)
-    SRCDSP_UPMIX_PP(8, 16)
-#undef SRCDSP_UPMIX_PP
-    switch (u0.L) {
-    case 2: SRCDSP_UPMIX(2, 0); break;
-    case 3: SRCDSP_UPMIX(3, 0); break;
-    case 4: SRCDSP_UPMIX(4, 0); break;
-    case 5: SRCDSP_UPMIX(5, 0); break;
-    case 6: SRCDSP_UPMIX(6, 0); break;
-    case 7: SRCDSP_UPMIX(7, 0); break;
-    default: SRCDSP_UPMIX(8, 0); break;
-    }
-#undef SRCDSP_UPMIX
-    SRCDSP_HIP_TRY(hipGetLastError());
-    const unsigned long n_out = (unsigned long)u0.L * (unsigned long)n_total;
-    for (int c = 0; c < nc; ++c) {
-        MixerState &m = mixers[c]->m;
-        m.advance(n_out);
-        int rc = chan_commit(ups[c]->u, s);
-        if (!rc) rc = m.order.after(s);
-        if (rc) return rc;
-    }
-    return SRCDSP_OK;
+    size_t smem = 0;
+    int rc = upmix_launch_begin(P, ups, mixers, nc, d_out, out_stride, n_in, n_total, iter, s, &smem, upmix_no_more);
+    if (rc) return rc;
+    const dim3 grid((unsigned)up_tiles(n_total), (unsigned)nc);
+    const bool served = up_dot2_dispatch<UpDot2Standard>(u0.L, (u0.H + 1) / 2, [&](auto lr, auto ppc) {
+        hipLaunchKernelGGL((upmix_tile_dot2<decltype(lr)::value, decltype(ppc)::value>), grid, dim3(kUpBlockD), smem, s,
+                           P);
+    });
+    rc = up_dot2_launched(served);
+    if (rc) return rc;
+    return upmix_launch_commit(ups, mixers, nc, n_total, s, upmix_no_more);
 }
 
 // one chain; *fused tells which path served it (untouched when nothing ran)

@@ -283,47 +283,16 @@ static int up_launch(srcdsp_up_state &u, const void *d_in, size_t n_in, void *d_
     const bool dot2_l = u.L >= 2 && u.L <= 8;  // up_tile_dot2: LR in 2..8
     if (u.variant == UV_CI16_I32 && u.coef_i16 && dot2_l && u.ntaps <= kUpMaxTaps && ((uintptr_t)d_in & 15u) == 0 &&
         ((uintptr_t)d_out & 15u) == 0) {
-        constexpr int TI = kUpRD * kUpBlockD;
-        const int PP = (u.H + 1) / 2, HG = (PP + 3) / 4, PGR = TI / 8 + HG;
-        const size_t out_lds = 16 * (size_t)kUpBlockD * (kUpRD * u.L / 4 + 1);  // staged output tile
-        const size_t smem = std::max(4 * 16 * (size_t)PGR, out_lds);
-        const dim3 grid((unsigned)((n_total + TI - 1) / TI));
-        // non-temporal output stores: 0.414 -> 0.385 ms at L = 4, 128 taps, 2^26 inputs
-#define SRCDSP_UP_DOT2(LR)                                                                                        \
-    hipLaunchKernelGGL((up_tile_dot2<LR, true, WSV, MW, PPV>), grid, dim3(kUpBlockD), smem, s, (const uint32_t *)d_in, (long)n_in, \
-                       n_total, (const uint32_t *)hin0, (uint32_t *)hout0, u.d_pair, u.H, shift, (uint32_t *)d_out)
-        // 16, 32 or 64 taps per phase (L = 4 x 64 / 128 / 256 taps, L = 2 x 32 /
-        // 64 / 128): compile-time shapes
-#define SRCDSP_UP_PP(LR, P)                              \
-    if (u.L == LR && PP == P) {                          \
-        constexpr int WSV = 3, MW = 1, PPV = P;          \
-        SRCDSP_UP_DOT2(LR);                              \
-    } else
-        SRCDSP_UP_PP(2, 8)
-        SRCDSP_UP_PP(2, 16)
-        SRCDSP_UP_PP(2, 32)
-        SRCDSP_UP_PP(4, 8)
-        SRCDSP_UP_PP(4, 16)
-        SRCDSP_UP_PP(4, 32)
-        SRCDSP_UP_PP(8, 8)
-        SRCDSP_UP_PP(8, 16)
-#undef SRCDSP_UP_PP
-        if (u.L == 2) {
-            constexpr int WSV = 3, MW = 1, PPV = 0;
-            SRCDSP_UP_DOT2(2);
-        } else {
-            constexpr int WSV = 3, MW = 1, PPV = 0;
-            switch (u.L) {
-            case 3: SRCDSP_UP_DOT2(3); break;
-            case 4: SRCDSP_UP_DOT2(4); break;
-            case 5: SRCDSP_UP_DOT2(5); break;
-            case 6: SRCDSP_UP_DOT2(6); break;
-            case 7: SRCDSP_UP_DOT2(7); break;
-            default: SRCDSP_UP_DOT2(8); break;
-            }
-        }
-#undef SRCDSP_UP_DOT2
-        SRCDSP_HIP_TRY(hipGetLastError());
+        const size_t smem = up_dot2_smem(u.H, u.L);
+        const dim3 grid((unsigned)up_tiles(n_total));
+        const bool served = up_dot2_dispatch<UpDot2Standard>(u.L, (u.H + 1) / 2, [&](auto lr, auto ppc) {
+            // non-temporal output stores: 0.414 -> 0.385 ms at L = 4, 128 taps, 2^26 inputs
+            hipLaunchKernelGGL((up_tile_dot2<decltype(lr)::value, true, 3, 1, decltype(ppc)::value>), grid,
+                               dim3(kUpBlockD), smem, s, (const uint32_t *)d_in, (long)n_in, n_total,
+                               (const uint32_t *)hin0, (uint32_t *)hout0, u.d_pair, u.H, shift, (uint32_t *)d_out);
+        });
+        rc = up_dot2_launched(served);
+        if (rc) return rc;
         u.cur ^= 1;
         return u.order.after(s);
     }

@@ -1,10 +1,13 @@
 """CPU-side checks of the interpolator -> mixer chain entry points
 (srcdsp_upmix_step, srcdsp_upmix_step_batched, srcdsp_upmix_stats): exported,
 in the ctypes signature table, the argument rules that must refuse a call
-before any HIP call, and the fused kernel's gfx950 resources -- no GPU here."""
+before any HIP call, the fused kernel's gfx950 resources, and the shape
+dispatcher of the v_dot2 transmit tiles (up_dot2_dispatch.h) swept by a
+sanitized host program -- no GPU here."""
 import ctypes as C
 import os
 import re
+import shutil
 import subprocess
 import sys
 
@@ -98,3 +101,26 @@ def test_stats_are_zero_in_a_fresh_process(capi):
     r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     assert r.stdout.split() == ["0", "0", "0", "0"]
+
+
+def test_tile_shape_dispatcher_under_host_sanitizers(tmp_path):
+    """tests/cpp/up_dot2_dispatch_main.cpp: a stand-alone program over
+    up_dot2_dispatch.h, built with -fsanitize=address,undefined and run as a
+    program.  For the three families' shape tables, every L = 1..9 and PP =
+    1..2048: one call of the callback where the family has the ratio, none
+    otherwise, with the <LR, PPC> of a table written out a second time there;
+    15, 10 and 10 kernels are reached (the summing tile's 10 twice, with and
+    without staggers)."""
+    cxx = shutil.which("g++") or shutil.which("clang++")
+    assert cxx, "a host C++ compiler"
+    exe = str(tmp_path / "up_dot2_dispatch")
+    r = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined",
+                        "-fno-sanitize-recover=undefined",
+                        os.path.join(ROOT, "tests", "cpp", "up_dot2_dispatch_main.cpp"), "-o", exe],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    assert re.search(r"^55296 cases, 0 failures$", r.stdout, re.M), r.stdout  # 3 families x 9 L x 2048 PP
+    for family, n in (("standard", 15), ("resampler", 10), ("summing tile", 10)):
+        assert f"{family}: {n} kernels" in r.stdout, r.stdout
