@@ -207,6 +207,23 @@ SRCDSP_API int srcdsp_mixdecim_step_batched(const srcdsp_mixer_t *mixers, const 
 /* process-wide counters: calls served by the bank kernel, calls served by the per-channel loop */
 SRCDSP_API int srcdsp_mixdecim_batched_stats(unsigned long *bank_calls, unsigned long *loop_calls);
 
+/* Extension (test and measurement hook of the persistent streaming kernels
+ * behind srcdsp_decim_step, srcdsp_fir_step, srcdsp_mixdecim_step and their
+ * batched forms: dnsampling_filters.h:129-172, filters.h:131-169,
+ * mixers.h:169-188).  Those kernels run on min(tiles of the call, a measured
+ * product grid) workgroups, each walking its share of the tiles.  cap >= 1
+ * makes every such launch use min(its product grid, cap) workgroups in x, so
+ * that a short call gives every workgroup several tiles; 0 puts the product
+ * grids back; negative is SRCDSP_ERR_ARG.  Process-wide.  Results do not
+ * depend on it; speed does. */
+SRCDSP_API int srcdsp_stream_set_grid_cap(long cap);
+/* Extension: the cap as last set (0: the product grids) */
+SRCDSP_API long srcdsp_stream_get_grid_cap(void);
+/* Extension.  Process-wide counters: launches of the persistent streaming
+ * kernels, and those among them with more tiles than workgroups (some
+ * workgroup walked more than one tile).  Null pointers are skipped. */
+SRCDSP_API int srcdsp_stream_grid_stats(unsigned long *launches, unsigned long *looping);
+
 /* FilterUpsamplingFir (variant 0 or 1) -> Mixer fused, the transmit chain: the
  * two reference calls up.step(in, tmp, flush) (upsampling_filters.h:149-233;
  * iterator=1: the iterator overload's shift 0, :240-323); mixer.step(tmp, out)

@@ -12,6 +12,7 @@ import re
 PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 LIB_PATH = os.environ.get("SRCDSP_HIP_LIB", os.path.join(PKG, "lib", "libsrcdsp_hip.so"))
+LIB_NAMED = "SRCDSP_HIP_LIB" in os.environ  # not the shipped build: see lib()
 HEADER = os.path.join(ROOT, "include", "srcdsp_hip.h")
 
 VP, I, U, SZ, F, D = C.c_void_p, C.c_int, C.c_uint, C.c_size_t, C.c_float, C.c_double
@@ -63,6 +64,9 @@ SIGNATURES = {
     "srcdsp_mixdecim_step": (I, [VP, VP, VP, SZ, VP, SZ, VP]),
     "srcdsp_mixdecim_step_batched": (I, [HP, HP, I, VP, SZ, VP, SZ, SZ, VP]),
     "srcdsp_mixdecim_batched_stats": (I, [C.POINTER(C.c_ulong), C.POINTER(C.c_ulong)]),
+    "srcdsp_stream_set_grid_cap": (I, [C.c_long]),
+    "srcdsp_stream_get_grid_cap": (C.c_long, []),
+    "srcdsp_stream_grid_stats": (I, [C.POINTER(C.c_ulong), C.POINTER(C.c_ulong)]),
     "srcdsp_upmix_step": (I, [VP, VP, VP, SZ, VP, SZ, I, I, VP]),
     "srcdsp_upmix_step_batched": (I, [HP, HP, I, VP, SZ, VP, SZ, SZ, I, VP]),
     "srcdsp_upmix_stats": (I, [C.POINTER(C.c_ulong)] * 4),
@@ -211,8 +215,17 @@ def lib() -> C.CDLL:
         raise ImportError(f"libsrcdsp_hip.so not built at {LIB_PATH}: run `python -m srcdsp_amd.build` "
                           "(hipcc, gfx950). There is no CPU fallback.")
     lib_ = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
+    # The shipped library exports every entry point of the table, or loading it
+    # fails here.  A build named by SRCDSP_HIP_LIB (an A/B base, a test variant)
+    # may be of an older tree: an entry point it lacks is left unbound and the
+    # call that needs it raises AttributeError naming it.
     for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib_, name)
+        try:
+            fn = getattr(lib_, name)
+        except AttributeError:
+            if not LIB_NAMED:
+                raise
+            continue
         fn.restype = res
         fn.argtypes = args
     _LIB = lib_

@@ -29,7 +29,7 @@ template <int NT, int M = 4>
 int launch_cf32(DecimLaunch L, int channels, bool fma, hipStream_t s) {
     constexpr int R = cf32_r<M>(), TO = kCfBlock * R;
     L.ntiles = (L.n_out + TO - 1) / TO;
-    dim3 grid((unsigned)std::min<long>(L.ntiles, kCfGrid), channels);
+    dim3 grid(persistent_grid(L.ntiles, kCfGrid), channels);
     const bool q0 = (L.shift & 31u) == 0;  // limitScale16 shift 0: the 4-op float quantiser
     const size_t smem = NT == 0 ? 16 * (size_t)cf32_lds_granules(M, R, kCfBlock, L.ntaps) : 0;
     // measured best (scripts/tune, sustained back-to-back): 512-lane tiles

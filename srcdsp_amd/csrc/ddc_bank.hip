@@ -61,10 +61,11 @@ int bank_launch(const srcdsp_mixer_t *mixers, const srcdsp_decim_t *decims, int 
     L.channels = nc;
     // a shared input: a workgroup serves a group of channels from one fetch of
     // the tile; the group shrinks while the grid would not fill the device
+    const long grid_cap = stream_grid_cap(kBankGridCap);
     int group = 1;
     if (in_stride == 0) {
         group = std::min(kBankGroup, nc);
-        while (group > 1 && L.ntiles * ((nc + group - 1) / group) < kBankGridCap / 2) group = (group + 1) / 2;
+        while (group > 1 && L.ntiles * ((nc + group - 1) / group) < grid_cap / 2) group = (group + 1) / 2;
     }
     L.group = group;
     const int ngroups = (nc + group - 1) / group;
@@ -75,7 +76,7 @@ int bank_launch(const srcdsp_mixer_t *mixers, const srcdsp_decim_t *decims, int 
         if (rc) return rc;
         L.mix[c] = m.word();
     }
-    dim3 grid((unsigned)std::min<long>(L.ntiles, std::max<long>(1, kBankGridCap / ngroups)), (unsigned)ngroups);
+    dim3 grid(persistent_grid(L.ntiles, std::max<long>(1, grid_cap / ngroups)), (unsigned)ngroups);
     hipLaunchKernelGGL(ddc_bank_ci16, grid, dim3(kBankBlock), 0, s, L);
     SRCDSP_HIP_TRY(hipGetLastError());
     for (int c = 0; c < nc; ++c) {

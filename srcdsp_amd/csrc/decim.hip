@@ -72,7 +72,7 @@ template <int NT>
 int launch_ci16(DecimLaunch L, int channels, bool mixed, hipStream_t s) {
     constexpr int TO = kCiBlock * kCiR;
     L.ntiles = (L.n_out + TO - 1) / TO;
-    dim3 grid((unsigned)std::min<long>(L.ntiles, kCfGridCap), channels);
+    dim3 grid(persistent_grid(L.ntiles, kCfGridCap), channels);
     if (mixed) {
         set_mix_geometry(L, ci16_halo(NT), ci16_spt(kCiBlock, kCiR));
         hipLaunchKernelGGL((decim_stream_ci16<NT, kCiR, kCiBlock, true, 4>), grid, dim3(kCiBlock), 0, s, L);
@@ -109,7 +109,7 @@ template <int NT, int BLOCK, int TABM, int MD = 4>
 int launch_ci16_dot2_shape(DecimLaunch L, int channels, bool mixed, hipStream_t s) {
     constexpr int SPT = dot2_spt(BLOCK, MD), TO = SPT / MD;  // input samples / outputs per tile
     L.ntiles = (L.n_out + TO - 1) / TO;
-    dim3 grid((unsigned)std::min<long>(L.ntiles, kCfGridCap * 256 / BLOCK), channels);
+    dim3 grid(persistent_grid(L.ntiles, kCfGridCap * 256 / BLOCK), channels);
     // M = 1 (16 outputs per lane) needs more than 128 VGPRs: 3 waves per SIMD
     constexpr int MINW = MD == 1 ? 3 : 4;
     if constexpr (TABM != 0) {
@@ -158,8 +158,8 @@ int launch_fir_tile(const DecimLaunch &L0, int channels, bool fma, hipStream_t s
     L.ntiles = (L.n_out + TO - 1) / TO;
     if (L.ntaps <= kFirStreamTaps) {  // persistent, prefetching
         // grid 512..2048 measure alike (0.650-0.660 ms, 2^28 samples, 31 taps); 256 is 1.7x slower
-        dim3 grid((unsigned)std::min<long>(L.ntiles, kCfGridCap), channels);
-#define SRCDSP_FIR_STREAM(NTC)                                                               \
+        dim3 grid(persistent_grid(L.ntiles, kCfGridCap), channels);
+#define SRCDSP_FIR_STREAM(NTC)                                                              \
     if (fma)                                                                                 \
         hipLaunchKernelGGL((fir_stream_f32<KV, true, 2, NTC>), grid, dim3(kFirBlock), 0, s, L); \
     else                                                                                     \

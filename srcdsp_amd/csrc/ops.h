@@ -24,6 +24,18 @@ inline int raise_lds_limit(const void *kern, size_t bytes) {
     return SRCDSP_OK;
 }
 
+// The persistent streaming kernels (decim_stream_cf32, decim_stream_ci16,
+// decim_dot2_ci16, fir_stream_f32, ddc_bank_ci16) run on min(tiles, a measured
+// product grid) workgroups in x.  srcdsp_stream_set_grid_cap lowers that grid
+// for tests and measurements (results do not depend on it), so a short call
+// gives every workgroup several tiles.
+// stream_grid_cap: the grid a launcher's product value stands for under the cap.
+// persistent_grid: the x grid of one launch of `ntiles` tiles, counted for
+// srcdsp_stream_grid_stats (a launch "loops" when it has more tiles than
+// workgroups).
+long stream_grid_cap(long product);
+unsigned persistent_grid(long ntiles, long product);
+
 // Kernel-level sample/coefficient combinations.  Decimator variants 0-3 map
 // 1:1; FilterFir variant 1 (float in, float taps, complex<float> out with a
 // zero imaginary part) is KV_F32_REAL.

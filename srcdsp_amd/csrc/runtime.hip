@@ -3,7 +3,7 @@
 // reference constructors, stream ordering, pinned staging, the batched entry
 // points' shared frame (bank_host.h), and the synthetic sample generator used
 // by benchmarks.
-#include "common.h"
+#include "ops.h"
 
 #include <algorithm>
 #include <condition_variable>
@@ -207,6 +207,24 @@ void GrowBuf::destroy() {
     cap = 0;
 }
 
+// ------------------------------------------------- persistent grids (ops.h)
+namespace {
+std::atomic<long> g_grid_cap{0};  // > 0: set by srcdsp_stream_set_grid_cap
+PathCounter g_stream_launches, g_stream_looping;
+}  // namespace
+
+long stream_grid_cap(long product) {
+    const long cap = g_grid_cap.load(std::memory_order_relaxed);
+    return cap > 0 ? std::min(product, cap) : product;
+}
+
+unsigned persistent_grid(long ntiles, long product) {
+    const long grid = std::min(ntiles, stream_grid_cap(product));
+    g_stream_launches.hit();
+    if (ntiles > grid) g_stream_looping.hit();
+    return (unsigned)grid;
+}
+
 int sample_bytes(int kind) {
     switch (kind) {
     case 0: return 8;
@@ -246,6 +264,20 @@ extern "C" {
 
 SRCDSP_API const char *srcdsp_last_error(void) { return get_error(); }
 SRCDSP_API const char *srcdsp_version(void) { return "0.1.0 gfx950"; }
+
+SRCDSP_API int srcdsp_stream_set_grid_cap(long cap) {
+    SRCDSP_ARG_CHECK(cap >= 0, "stream_set_grid_cap: cap is >= 1, or 0 for the product grids");
+    g_grid_cap.store(cap, std::memory_order_relaxed);
+    return SRCDSP_OK;
+}
+
+SRCDSP_API long srcdsp_stream_get_grid_cap(void) { return g_grid_cap.load(std::memory_order_relaxed); }
+
+SRCDSP_API int srcdsp_stream_grid_stats(unsigned long *launches, unsigned long *looping) {
+    g_stream_launches.read(launches);
+    g_stream_looping.read(looping);
+    return SRCDSP_OK;
+}
 
 SRCDSP_API int srcdsp_fill_synthetic(void *d_out, int kind, size_t n, uint64_t seed, uint64_t channel,
                                      uint64_t offset, int lo, int hi, void *stream) {

@@ -429,6 +429,27 @@ def mixdecim_batched_stats():
     return b.value, l.value
 
 
+def stream_set_grid_cap(cap: int):
+    """Test and measurement hook: every launch of a persistent streaming kernel
+    (the decimators, FilterFir on float input, the DDC bank) uses at most ``cap``
+    workgroups in x, so a short call gives every workgroup several tiles
+    (0: the product grids).  Process-wide; results do not depend on it."""
+    A.call("srcdsp_stream_set_grid_cap", int(cap))
+
+
+def stream_get_grid_cap() -> int:
+    """The cap as last set by stream_set_grid_cap (0: the product grids)."""
+    return int(A.lib().srcdsp_stream_get_grid_cap())
+
+
+def stream_grid_stats():
+    """(launches, looping): launches of the persistent streaming kernels, and
+    those with more tiles than workgroups, process-wide."""
+    a, b = C.c_ulong(), C.c_ulong()
+    A.call("srcdsp_stream_grid_stats", C.byref(a), C.byref(b))
+    return a.value, b.value
+
+
 class UpsamplerMixerChain:
     """up.step(in, tmp, flush); mixer.step(tmp, out) fused into one device pass
     (the transmit chain).  Both operators' state advances exactly as the two

@@ -2,7 +2,14 @@
 one call, on a shared input or one input per channel.  Every comparison is
 bit-exact against the two oracle calls per channel (mixers.h:169-188,
 dnsampling_filters.h:129-172), the mixer state included; the process-wide
-counters prove which path (bank kernel / per-channel loop) served a call."""
+counters prove which path (bank kernel / per-channel loop) served a call.
+
+What these calls reach of the kernel: 18 to 512 tiles of 4096 samples and at
+most 8 channels fill less than half of the 2048-workgroup grid, so the launcher
+shrinks the channel group to 1 and every workgroup takes one tile of one
+channel.  The channel loop with a group of up to 8 on one fetch, the partial
+last group and a workgroup's walk over several tiles are in
+test_gpu_stream_loops.py (under srcdsp_stream_set_grid_cap)."""
 import numpy as np
 import pytest
 

@@ -63,9 +63,11 @@ def _chunks(total, sizes):
                                      (1, 63), (1, 64), (1, 127), (1, 128), (3, 63), (3, 64), (3, 127), (3, 128),
                                      (16, 127), (16, 128), (16, 255), (16, 256)])
 def test_decim_cf32_tile_kernel_vs_oracle(S, O, fp, M, ntaps):
-    """The headline kernel at every (M, tap count) it is compiled for: many
-    tiles, tail tiles, history carried over uneven calls (incl. calls shorter
-    than a tile)."""
+    """The headline kernel at every (M, tap count) it is compiled for: calls
+    of up to 98 tiles with a tail tile, history carried over uneven calls
+    (incl. calls shorter than a tile).  That is under the 1024-workgroup grid,
+    so every workgroup takes exactly one tile; the grid-stride loop that
+    prefetches a workgroup's next tile is in test_gpu_stream_loops.py."""
     from srcdsp_amd.design import hamming_sinc
     c = hamming_sinc(ntaps - (ntaps % 2 == 0))
     if ntaps % 2 == 0:  # an even count: a trailing zero tap, as the 128-tap form of the 127-tap filter
