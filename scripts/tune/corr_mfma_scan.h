@@ -18,8 +18,8 @@
 //   before it left in a small seam array;
 // * early exit: a workgroup stops at the first tile that starts after a
 //   recorded hit (the first detection is the atomicMin over all hits, so no
-//   hit past it matters); the registers after the call come from corr_point,
-//   as on the product's fused path.
+//   hit past it matters); the registers after the call come from the
+//   step's tail (corr_step_tail, csrc/corr_tail.h), as on the product's fused path.
 // Per-sample HBM traffic is the 4 B input read (no per-sample scratch).
 // * one limb: each wave owns two 32 x 32 output blocks (RB = 2, 16 k-output
 //   tiles), so each B fragment read feeds two MFMAs (the probe's CORR_ROWB = 2:

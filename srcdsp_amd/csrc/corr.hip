@@ -9,9 +9,13 @@
 //                    as the reference's complex<int32_t>/uint32 registers);
 //   2. corr_detect : the 3-point peak + threshold test of correlators.h:262-268
 //                    on each index, reduced to the FIRST index with atomicMin;
-//   3. host        : state update -- the registers, the N*S-1 sample history
-//                    (the detected sample is dropped: the reference `break`s
-//                    without advancing `top`, correlators.h:291), bitSamples.
+//   3. corr_step_tail : the state update, on the device (corr_tail.h) -- the
+//                    registers, the N*S-1 sample history (the detected sample
+//                    is dropped: the reference `break`s without advancing
+//                    `top`, correlators.h:291), bitSamples; the host copies one
+//                    result row back (and the bitSamples row on a detection)
+//                    and commits it to the handle.
+// At S == 1 steps 1 and 2 are one launch, corr_scan_s1 (corr_scan_kernels.h).
 // The double-precision threshold sqrt(c) > sqrt(e)*2.7 is evaluated exactly:
 // sqrt(e) > 300 <=> e > 90000 for integer e, and the correctly rounded sqrt of
 // a uint32 is obtained from the hardware estimate by an exact 128-bit
@@ -23,7 +27,8 @@
 #include "fir_device.h"
 #include "corr_hit.h"
 #include "corr_state.h"         // the handle, corr_fetch, the dot2 tile geometry
-#include "corr_scan_kernels.h"  // the fused scan's tile and corr_point's arithmetic (shared with corr_bank.hip)
+#include "corr_scan_kernels.h"  // the fused scan's tile (shared with corr_bank.hip and corr_all.hip)
+#include "corr_tail.h"          // the end of a step (shared with corr_bank.hip) and the host commit
 
 namespace srcdsp {
 
@@ -253,24 +258,26 @@ __global__ void corr_detect(const uint32_t *__restrict__ corr, const uint32_t *_
     }
 }
 
-// new_hist[k] = effective stream sample (last - NSm1 + 1 + k), from input or old history
-__global__ void corr_history(const uint32_t *in, const uint32_t *hist_in, uint32_t *hist_out, long last,
-                             long NSm1) {
-    for (long k = (long)blockIdx.x * blockDim.x + threadIdx.x; k < NSm1; k += (long)gridDim.x * blockDim.x)
-        hist_out[k] = corr_fetch(in, hist_in, last - NSm1 + 1 + k, NSm1);
-}
-
-// the registers after a fused scan: corr_point_regs (corr_scan_kernels.h) at *best
-__global__ __launch_bounds__(256) void corr_point(const uint32_t *__restrict__ in, long n,
-                                                  const uint32_t *__restrict__ hist,
-                                                  const int32_t *__restrict__ coef, unsigned N, unsigned S, unsigned cs,
-                                                  const unsigned *__restrict__ best, uint32_t *__restrict__ out) {
-    corr_point_regs(in, n, hist, coef, N, S, cs, *best, out);
+// the end of every single-channel step and of priming: corr_tail (corr_tail.h)
+// at *best, the history and bitSamples copies spread over the grid
+struct CorrPrev {
+    uint32_t w[6];  // corr[0..2], energy[0..2] carried from the previous call
+};
+__global__ __launch_bounds__(kCorrTailBlock) void corr_step_tail(const uint32_t *__restrict__ in, long n,
+                                                                 const uint32_t *__restrict__ hist,
+                                                                 uint32_t *__restrict__ hist_out,
+                                                                 const int32_t *__restrict__ coef, unsigned N,
+                                                                 unsigned S, unsigned cs, const CorrPrev prev,
+                                                                 const unsigned *__restrict__ best,
+                                                                 uint32_t *__restrict__ row,
+                                                                 uint32_t *__restrict__ bits) {
+    corr_tail(in, n, hist, hist_out, coef, N, S, cs, prev.w, *best, row, bits, blockIdx.x, gridDim.x);
 }
 
 // ---------------------------------------------------------------- host side
-// detect = false: stream the samples with no detection test (corr_prime):
-// only the last three positions are evaluated (they feed the registers).
+// scan = false: stream the samples with no detection test (corr_prime): no
+// scan at all, `best` stays kCorrNone and the tail leaves the registers and
+// the history of the last sample.
 // trace (CREATE_DEBUG_FILES, correlators.h:253-257): host arrays of n_
 // entries receive corrValue[0] / energyValue[0] after each processed sample
 // (*trace_n of them: corrIndex + 2 on a detection, else n_); the segmented
@@ -281,7 +288,7 @@ struct CorrTrace {
 };
 
 static int corr_run(srcdsp_corr_state &c, const uint32_t *d_in, size_t n_, int *found, int *corr_index,
-                    hipStream_t s, bool detect = true, const CorrTrace *trace = nullptr) {
+                    hipStream_t s, bool scan = true, const CorrTrace *trace = nullptr) {
     *found = 0;
     if (trace) *trace->count = 0;
     if (n_ == 0) return SRCDSP_OK;
@@ -290,7 +297,12 @@ static int corr_run(srcdsp_corr_state &c, const uint32_t *d_in, size_t n_, int *
         set_error("corr_step: input longer than INT_MAX samples (correlators.h:212 uses int)");
         return SRCDSP_ERR_SIZE;
     }
-    int rc = c.order.before(s);
+    // the tail's results: a result row and a bitSamples row on the device, and their pinned mirror
+    int rc = c.bank.reserve(4 * (kCorrRow + (size_t)c.N));
+    if (rc) return rc;
+    uint32_t *const d_row = c.bank.dev<uint32_t>(), *const d_bits = d_row + kCorrRow;
+    uint32_t *const h_row = c.bank.host<uint32_t>(), *const h_bits = h_row + kCorrRow;
+    rc = c.order.before(s);
     if (rc) return rc;
     const long NSm1 = (long)c.NS - 1;
     const uint32_t *hist = c.d_hist[c.cur];
@@ -301,39 +313,32 @@ static int corr_run(srcdsp_corr_state &c, const uint32_t *d_in, size_t n_, int *
     // and every N <= kCorrDot2MaxTaps) one launch scans with detection fused
     const bool dot2 = c.taps16 && c.NP <= kCorrDot2MaxTaps && c.S <= kCorrMaxGridY &&
                       (c.N >= 48 || c.S == 1);
-    const bool fast = dot2 && c.S == 1;
-    // the fused scan keeps no per-sample values (corr_point computes the three
-    // the registers need); the segmented kernels write corr/energy per sample
-    // for corr_detect
-    const bool fused = fast && detect && !trace;
-    if (!fused) {
+    // the fused scan keeps no per-sample values, which a trace needs: the
+    // segmented kernels write corr/energy per sample for corr_detect
+    const bool fused = dot2 && c.S == 1 && !trace;
+    if (scan && !fused) {
         rc = c.corr_vals.reserve(4 * n_);
         if (!rc) rc = c.en_vals.reserve(4 * n_);
         if (rc) return rc;
     }
     uint32_t *const d_corr = c.corr_vals.dev<uint32_t>(), *const d_en = c.en_vals.dev<uint32_t>();
-    // The reference stops at the first detection (break, correlators.h:291).
-    // All segments are queued at once; each launch returns at its start when
-    // an earlier segment's detect kernel has recorded a hit, so the scan stops
-    // one segment after the detection with no host round trip in between.
-    const long seg = std::max<long>(1L << 22, (n + 15) / 16);
-    const unsigned none = 0xffffffffu;
-    unsigned best = none;
     SRCDSP_HIP_TRY(hipMemsetAsync(c.d_best, 0xff, 4, s));
-    if (fused) {  // one launch, detection fused, in-flight early exit
+    if (scan && fused) {  // one launch, detection fused, in-flight early exit
         constexpr long TO = (long)kCBlock * kCR;
         const long blocks = (n + TO - 1) / TO;
         const size_t smem = 4 * (size_t)corr_scan_lds_words((int)c.NP);
         hipLaunchKernelGGL(corr_scan_s1, dim3((unsigned)blocks), dim3(kCBlock), smem, s, d_in, n, hist, c.d_ptaps,
                            (int)c.N, (int)c.NP, cs, c.corr[0], c.corr[1], c.energy[0], c.d_best);
         SRCDSP_HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(corr_point, dim3(1), dim3(256), 0, s, d_in, n, hist, c.d_coef, c.N, c.S, cs,
-                           (const unsigned *)c.d_best, c.d_best + 2);
-        SRCDSP_HIP_TRY(hipGetLastError());
     }
-    // the segmented path: priming (the last 3 positions only) and the generic
-    // kernels (S > 1 or N % 16 != 0)
-    for (long sb = detect ? (fused ? n : 0) : std::max(0L, n - 3); sb < n; sb += seg) {
+    // The segmented path: S > 1, patterns past the int16 range or past
+    // kCorrDot2MaxTaps taps, and the traces.
+    // The reference stops at the first detection (break, correlators.h:291).
+    // All segments are queued at once; each launch returns at its start when
+    // an earlier segment's detect kernel has recorded a hit, so the scan stops
+    // one segment after the detection with no host round trip in between.
+    const long seg = std::max<long>(1L << 22, (n + 15) / 16);
+    for (long sb = scan && !fused ? 0 : n; sb < n; sb += seg) {
         const long se = std::min(n, sb + seg);
         if (dot2) {  // grid.y = phase of the stride
             constexpr long TO = (long)kCBlock * kCR;
@@ -354,95 +359,30 @@ static int corr_run(srcdsp_corr_state &c, const uint32_t *d_in, size_t n_, int *
                                    c.d_coef, c.N, c.S, cs, d_corr, d_en, (const unsigned *)c.d_best);
         }
         SRCDSP_HIP_TRY(hipGetLastError());
-        if (!detect) continue;
         const int db = (int)std::max<long>(1, std::min<long>((se - sb + 255) / 256, 4096));
         hipLaunchKernelGGL(corr_detect, dim3(db), dim3(256), 0, s, d_corr, d_en, sb, se, c.corr[0], c.corr[1],
                            c.energy[0], c.d_best);
         SRCDSP_HIP_TRY(hipGetLastError());
     }
-    unsigned words[8];  // best, pad, corr_point's corr[3] and energy[3]
-    SRCDSP_HIP_TRY(hipMemcpyAsync(words, c.d_best, fused ? sizeof words : 4, hipMemcpyDeviceToHost, s));
+    // the tail: workgroup 0 the registers and the row, all of them the history and bitSamples copies
+    const CorrPrev prev{{c.corr[0], c.corr[1], c.corr[2], c.energy[0], c.energy[1], c.energy[2]}};
+    const long copy = std::max<long>(NSm1, c.N);
+    const unsigned tb = (unsigned)std::min<long>((copy + kCorrTailBlock - 1) / kCorrTailBlock, 1024);
+    hipLaunchKernelGGL(corr_step_tail, dim3(tb), dim3(kCorrTailBlock), 0, s, d_in, n, hist, c.d_hist[c.cur ^ 1],
+                       (const int32_t *)c.d_coef, c.N, c.S, cs, prev, (const unsigned *)c.d_best, d_row, d_bits);
+    SRCDSP_HIP_TRY(hipGetLastError());
+    SRCDSP_HIP_TRY(hipMemcpyAsync(h_row, d_row, 4 * kCorrRow, hipMemcpyDeviceToHost, s));
     SRCDSP_HIP_TRY(hipStreamSynchronize(s));
-    best = words[0];
-
-    const bool hit = best != none;
-    const long last = hit ? (long)best : n - 1;  // last processed sample
+    const bool hit = h_row[0] != kCorrNone;
+    if (hit) SRCDSP_HIP_TRY(hipMemcpyAsync(h_bits, d_bits, 4 * (size_t)c.N, hipMemcpyDeviceToHost, s));
     if (trace) {  // every processed sample's registers (the segmented kernels computed them all up to `last`)
-        SRCDSP_HIP_TRY(hipMemcpyAsync(trace->corr, d_corr, 4 * (size_t)(last + 1), hipMemcpyDeviceToHost, s));
-        SRCDSP_HIP_TRY(hipMemcpyAsync(trace->energy, d_en, 4 * (size_t)(last + 1), hipMemcpyDeviceToHost, s));
-        SRCDSP_HIP_TRY(hipStreamSynchronize(s));
-        *trace->count = (size_t)(last + 1);
+        const size_t cnt = hit ? (size_t)h_row[0] + 1 : n_;
+        SRCDSP_HIP_TRY(hipMemcpyAsync(trace->corr, d_corr, 4 * cnt, hipMemcpyDeviceToHost, s));
+        SRCDSP_HIP_TRY(hipMemcpyAsync(trace->energy, d_en, 4 * cnt, hipMemcpyDeviceToHost, s));
+        *trace->count = cnt;
     }
-    // registers after processing `last` (correlators.h:228-230, 248-250)
-    uint32_t cw[3] = {0, 0, 0}, ew[3] = {0, 0, 0};
-    const long lo = std::max(0L, last - 2);
-    const long cnt = last - lo + 1;
-    if (fused) {
-        for (long idx = lo; idx <= last; ++idx) {
-            cw[idx - lo] = words[2 + (last - idx)];
-            ew[idx - lo] = words[5 + (last - idx)];
-        }
-    } else {
-        SRCDSP_HIP_TRY(hipMemcpyAsync(cw, d_corr + lo, 4 * cnt, hipMemcpyDeviceToHost, s));
-        SRCDSP_HIP_TRY(hipMemcpyAsync(ew, d_en + lo, 4 * cnt, hipMemcpyDeviceToHost, s));
-        SRCDSP_HIP_TRY(hipStreamSynchronize(s));
-    }
-    uint32_t nc[3], ne[3];
-    for (int k = 0; k < 3; ++k) {  // nc[k] = corr of sample last-k
-        long idx = last - k;
-        if (idx >= 0) {
-            nc[k] = cw[idx - lo];
-            ne[k] = ew[idx - lo];
-        } else {  // reach back into the previous registers
-            nc[k] = c.corr[-idx - 1];
-            ne[k] = c.energy[-idx - 1];
-        }
-    }
-    if (hit) {
-        // bitSamples (correlators.h:278-288): ring read backwards from the peak
-        // sample best-1 with stride S; with S == 1 the oldest slot already
-        // holds the detected sample (the ring wrapped onto it).
-        std::vector<uint32_t> win((size_t)c.NS + 1);
-        // effective stream positions best-NS .. best
-        const long first = (long)best - (long)c.NS;
-        std::vector<uint32_t> h_hist(NSm1 > 0 ? NSm1 : 1);
-        if (NSm1 > 0) SRCDSP_HIP_TRY(hipMemcpyAsync(h_hist.data(), hist, 4 * NSm1, hipMemcpyDeviceToHost, s));
-        const long in_lo = std::max(0L, first);
-        const long in_cnt = (long)best - in_lo + 1;
-        std::vector<uint32_t> h_in(in_cnt);
-        SRCDSP_HIP_TRY(hipMemcpyAsync(h_in.data(), d_in + in_lo, 4 * in_cnt, hipMemcpyDeviceToHost, s));
-        SRCDSP_HIP_TRY(hipStreamSynchronize(s));
-        for (long j = first; j <= (long)best; ++j) {
-            uint32_t v;
-            if (j >= 0) v = h_in[j - in_lo];
-            else v = (j + NSm1 >= 0) ? h_hist[j + NSm1] : 0u;
-            win[j - first] = v;
-        }
-        for (unsigned m = 0; m < c.N; ++m) {
-            const long d = (long)(c.N - 1 - m) * c.S;
-            uint32_t v = (d == NSm1) ? win[c.NS] : win[((long)best - 1 - d) - first];
-            c.bits[2 * m] = (int16_t)(v & 0xffff);
-            c.bits[2 * m + 1] = (int16_t)(v >> 16);
-        }
-    }
-    // history: last NS-1 samples of the effective stream (the detected sample is
-    // overwritten by the next call's first sample)
-    const long last_eff = hit ? (long)best - 1 : n - 1;
-    if (NSm1 > 0) {
-        const int hb = (int)std::max<long>(1, std::min<long>((NSm1 + 255) / 256, 1024));
-        hipLaunchKernelGGL(corr_history, dim3(hb), dim3(256), 0, s, d_in, hist, c.d_hist[c.cur ^ 1], last_eff, NSm1);
-        SRCDSP_HIP_TRY(hipGetLastError());
-        c.cur ^= 1;
-    }
-    for (int k = 0; k < 3; ++k) {
-        c.corr[k] = nc[k];
-        c.energy[k] = ne[k];
-    }
-    if (hit) {
-        *found = 1;
-        *corr_index = (int)best - 1;
-    }
-    return c.order.after(s);
+    if (hit || trace) SRCDSP_HIP_TRY(hipStreamSynchronize(s));
+    return corr_commit(c, h_row, h_bits, found, corr_index, s);
 }
 
 }  // namespace srcdsp
@@ -504,7 +444,7 @@ SRCDSP_API int srcdsp_corr_create(srcdsp_corr_t *out, unsigned N, unsigned S) {
     if (hipMalloc(&c.d_coef, 8 * (size_t)N) != hipSuccess || hipMemset(c.d_coef, 0, 8 * (size_t)N) != hipSuccess ||
         hipMalloc(&c.d_ptaps, 8 * (size_t)c.NP) != hipSuccess || hipMemset(c.d_ptaps, 0, 8 * (size_t)c.NP) != hipSuccess ||
         hipMalloc(&c.d_hist[0], hb) != hipSuccess || hipMalloc(&c.d_hist[1], hb) != hipSuccess ||
-        hipMemset(c.d_hist[0], 0, hb) != hipSuccess || hipMalloc(&c.d_best, 32) != hipSuccess) {
+        hipMemset(c.d_hist[0], 0, hb) != hipSuccess || hipMalloc(&c.d_best, 4) != hipSuccess) {
         set_error("corr_create: device allocation failed");
         srcdsp_corr_destroy(h);
         return SRCDSP_ERR_HIP;
@@ -628,10 +568,8 @@ SRCDSP_API int srcdsp_corr_step_host(srcdsp_corr_t h, const void *in, size_t n, 
     *found = 0;
     if (n == 0) return SRCDSP_OK;
     srcdsp_corr_state &c = h->c;
-    int rc = c.stage.reserve(4 * n, 4 * n);
+    const int rc = corr_stage_in(c, in, n);
     if (rc) return rc;
-    host_copy(c.stage.h_buf, in, 4 * n);
-    SRCDSP_HIP_TRY(hipMemcpyAsync(c.stage.d_buf, c.stage.h_buf, 4 * n, hipMemcpyHostToDevice, c.stage.stream));
     return corr_run(c, (const uint32_t *)c.stage.d_buf, n, found, corr_index, c.stage.stream);
 }
 
@@ -655,10 +593,8 @@ SRCDSP_API int srcdsp_corr_step_host_trace(srcdsp_corr_t h, const void *in, size
     *count = 0;
     if (n == 0) return SRCDSP_OK;
     srcdsp_corr_state &c = h->c;
-    int rc = c.stage.reserve(4 * n, 4 * n);
+    const int rc = corr_stage_in(c, in, n);
     if (rc) return rc;
-    host_copy(c.stage.h_buf, in, 4 * n);
-    SRCDSP_HIP_TRY(hipMemcpyAsync(c.stage.d_buf, c.stage.h_buf, 4 * n, hipMemcpyHostToDevice, c.stage.stream));
     const CorrTrace t{corr_out, energy_out, count};
     return corr_run(c, (const uint32_t *)c.stage.d_buf, n, found, corr_index, c.stage.stream, true, &t);
 }

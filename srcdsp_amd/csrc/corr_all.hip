@@ -11,9 +11,10 @@
 //   corr_all_resolve : one workgroup per channel runs the walk of
 //                      corr_all_walk.h over the bitmap -- accepts a candidate,
 //                      recomputes the patch after it on the stream with the
-//                      detected samples deleted, and finishes as
-//                      corr_bank_finish does (registers, new history, the
-//                      bitSamples row of every detection, one result row),
+//                      detected samples deleted, and finishes with a tail of
+//                      its own (registers, new history, the bitSamples row of
+//                      every detection, one result row: corr_tail's work, but
+//                      stepping over the deleted samples),
 // then one D2H copy of the result rows and detection lists and one of the
 // bitSamples rows: two host synchronisations at most, whatever the channel
 // count and the number of detections.  Every other shape runs the literal
@@ -23,6 +24,7 @@
 #include "ops.h"
 #include "corr_state.h"
 #include "corr_scan_kernels.h"
+#include "corr_tail.h"  // the per-channel argument block, the register commit
 #include "corr_all_walk.h"
 
 namespace srcdsp {
@@ -31,27 +33,21 @@ constexpr int kAllRow = 8;        // result row: hits, consumed, corr[3], energy
 constexpr int kAllBlock = 1024;   // lanes of a resolve workgroup = outputs per patch batch
 
 struct CorrAllArgs {
-    const uint32_t *in;  // channel c reads in + c * in_stride (0: one shared input)
-    long in_stride, n;
-    int N, NP, max_hits;
+    CorrChanArgs ch;
+    int max_hits;
     uint16_t *map;    // [channels][map_stride]: one bit per output, written whole by corr_all_map
     long map_stride;  // 16-bit words per channel (tiles * kCBlock)
     int *det;         // [channels][max_hits]: the detected samples, ascending
     uint32_t *res;    // [channels][kAllRow]
     uint32_t *bits;   // [channels][max_hits][N]
-    const uint32_t *hist[kMaxBatch];
-    uint32_t *hist_out[kMaxBatch];
-    const uint32_t *ptaps[kMaxBatch];
-    const int32_t *coef[kMaxBatch];
-    unsigned cs[kMaxBatch];
-    uint32_t prev[kMaxBatch][6];  // corr[0..2], energy[0..2] carried from the previous call
 };
 static_assert(sizeof(CorrAllArgs) <= 4096, "kernel arguments are limited to 4 KB");
 
 __global__ __launch_bounds__(kCBlock, SRCDSP_CORR_MINW) void corr_all_map(const CorrAllArgs A) {
     const int c = blockIdx.y;
-    corr_scan_tile<true>(A.in + (long)c * A.in_stride, A.n, A.hist[c], A.ptaps[c], A.N, A.NP, A.cs[c], A.prev[c][0],
-                         A.prev[c][1], A.prev[c][3], nullptr, (long)blockIdx.x, A.map + (long)c * A.map_stride);
+    const CorrChanArgs &H = A.ch;
+    corr_scan_tile<true>(H.in + (long)c * H.in_stride, H.n, H.hist[c], H.ptaps[c], H.N, H.NP, H.cs[c], H.prev[c][0],
+                         H.prev[c][1], H.prev[c][3], nullptr, (long)blockIdx.x, A.map + (long)c * A.map_stride);
 }
 
 // the walk's cooperative parts for one workgroup of kAllBlock lanes
@@ -158,33 +154,34 @@ struct CorrAllDev {
 };
 
 __global__ __launch_bounds__(kAllBlock) void corr_all_resolve(const CorrAllArgs A) {
+    const CorrChanArgs &H = A.ch;
     __shared__ uint32_t cb[kAllBlock], eb[kAllBlock];
     __shared__ unsigned found;
     const int c = blockIdx.x;
-    const uint32_t *in = A.in + (long)c * A.in_stride, *hist = A.hist[c];
+    const uint32_t *in = H.in + (long)c * H.in_stride, *hist = H.hist[c];
     int *det = A.det + (long)c * A.max_hits;
     CorrAllDev x;
     x.in = in;
     x.hist = hist;
-    x.coef = A.coef[c];
+    x.coef = H.coef[c];
     x.map64 = (const unsigned long long *)(A.map + (long)c * A.map_stride);
     x.nwords = A.map_stride / 4;
     x.det = det;
-    x.N = A.N;
-    x.cs = A.cs[c];
+    x.N = H.N;
+    x.cs = H.cs[c];
     for (int k = 0; k < 3; ++k) {
-        x.pc[k] = A.prev[c][k];
-        x.pe[k] = A.prev[c][3 + k];
+        x.pc[k] = H.prev[c][k];
+        x.pe[k] = H.prev[c][3 + k];
     }
     extern __shared__ __attribute__((aligned(16))) uint32_t win[];
-    x.ptaps = A.ptaps[c];
-    x.pad = A.NP - A.N;
+    x.ptaps = H.ptaps[c];
+    x.pad = H.NP - H.N;
     x.win = win;
     x.cb = cb;
     x.eb = eb;
     x.found = &found;
     CorrAllResult r;
-    corr_all_walk(x, A.n, A.N, A.max_hits, r);
+    corr_all_walk(x, H.n, H.N, A.max_hits, r);
     __syncthreads();  // det[] complete
     if (threadIdx.x == 0) {
         uint32_t *row = A.res + (long)kAllRow * c;
@@ -195,18 +192,18 @@ __global__ __launch_bounds__(kAllBlock) void corr_all_resolve(const CorrAllArgs 
             row[5 + k] = r.energy[k];
         }
     }
-    const long NSm1 = A.N - 1;
+    const long NSm1 = H.N - 1;
     // history: the last N - 1 samples processed and not deleted
-    uint32_t *ho = A.hist_out[c];
+    uint32_t *ho = H.hist_out[c];
     for (long k = threadIdx.x; k < NSm1; k += kAllBlock)
         ho[k] = corr_fetch(in, hist, corr_all_back(det, r.hits, r.consumed, NSm1 - k), NSm1);
     // bitSamples of every detection (correlators.h:278-288 at S = 1): the ring
     // read backwards from the peak sample; its oldest slot holds the detected sample
-    uint32_t *bo = A.bits + (long)c * A.max_hits * A.N;
-    for (long g = threadIdx.x; g < (long)r.hits * A.N; g += kAllBlock) {
-        const int h = (int)(g / A.N), m = (int)(g % A.N);
+    uint32_t *bo = A.bits + (long)c * A.max_hits * H.N;
+    for (long g = threadIdx.x; g < (long)r.hits * H.N; g += kAllBlock) {
+        const int h = (int)(g / H.N), m = (int)(g % H.N);
         const long q = det[h];
-        bo[g] = corr_fetch(in, hist, m == 0 ? q : corr_all_back(det, h, q, A.N - m), NSm1);
+        bo[g] = corr_fetch(in, hist, m == 0 ? q : corr_all_back(det, h, q, H.N - m), NSm1);
     }
 }
 
@@ -243,28 +240,13 @@ int all_kernels(const srcdsp_corr_t *hs, int channels, const uint32_t *d_in, siz
     for (int c0 = 0; c0 < channels; c0 += kMaxBatch) {
         const int nc = std::min(kMaxBatch, channels - c0);
         CorrAllArgs A{};
-        A.in = d_in + (size_t)c0 * in_stride;
-        A.in_stride = (long)in_stride;
-        A.n = n;
-        A.N = (int)N;
-        A.NP = (int)lead.NP;
+        corr_chan_args(A.ch, hs + c0, nc, d_in + (size_t)c0 * in_stride, in_stride, n);
         A.max_hits = (int)H;
         A.map = d_map + map_stride * c0;
         A.map_stride = (long)map_stride;
         A.det = d_det + H * c0;
         A.res = d_res + (size_t)kAllRow * c0;
         A.bits = d_bits + H * N * c0;
-        for (int k = 0; k < nc; ++k) {
-            srcdsp_corr_state &c = hs[c0 + k]->c;
-            hist_pair(c, A.hist[k], A.hist_out[k]);
-            A.ptaps[k] = c.d_ptaps;
-            A.coef[k] = c.d_coef;
-            A.cs[k] = (unsigned)c.coeff_scaling;
-            for (int q = 0; q < 3; ++q) {
-                A.prev[k][q] = c.corr[q];
-                A.prev[k][3 + q] = c.energy[q];
-            }
-        }
         hipLaunchKernelGGL(corr_all_map, dim3((unsigned)tiles, (unsigned)nc), dim3(kCBlock), smem, s, A);
         SRCDSP_HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(corr_all_resolve, dim3((unsigned)nc), dim3(kAllBlock), 4 * (N - 1 + kAllBlock), s, A);
@@ -287,11 +269,7 @@ int all_kernels(const srcdsp_corr_t *hs, int channels, const uint32_t *d_in, siz
         srcdsp_corr_state &c = hs[ch]->c;
         const uint32_t *row = h_res + (size_t)kAllRow * ch;
         const size_t k = row[0];
-        for (int q = 0; q < 3; ++q) {
-            c.corr[q] = row[2 + q];
-            c.energy[q] = row[5 + q];
-        }
-        if (N > 1) c.cur ^= 1;
+        corr_commit_regs(c, row);
         n_hits[ch] = (int)k;
         consumed[ch] = row[1];
         for (size_t q = 0; q < k; ++q) corr_index[(size_t)ch * max_hits + q] = h_det[ch * H + q] - 1;
@@ -387,10 +365,8 @@ SRCDSP_API int srcdsp_corr_step_all_host(srcdsp_corr_t h, const void *in, size_t
     if (n == 0 || n > 0x7fffffffUL || max_hits < 1 || !n_hits || !corr_index || !consumed)  // refused or empty: no staging
         return srcdsp_corr_step_all(h, in, n, max_hits, n_hits, corr_index, bits_host, consumed, nullptr);
     srcdsp_corr_state &c = h->c;
-    int rc = c.stage.reserve(4 * n, 4 * n);
+    const int rc = corr_stage_in(c, in, n);
     if (rc) return rc;
-    host_copy(c.stage.h_buf, in, 4 * n);
-    SRCDSP_HIP_TRY(hipMemcpyAsync(c.stage.d_buf, c.stage.h_buf, 4 * n, hipMemcpyHostToDevice, c.stage.stream));
     return srcdsp_corr_step_all(h, c.stage.d_buf, n, max_hits, n_hits, corr_index, bits_host, consumed,
                                 c.stage.stream);
 }

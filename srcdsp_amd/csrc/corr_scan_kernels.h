@@ -1,7 +1,8 @@
 // corr_scan_kernels.h -- the fused S == 1 correlator scan as device functions,
-// shared by corr_scan_s1 (corr.hip, one channel per launch) and corr_bank_s1
-// (corr_bank.hip, one channel per grid row), and the register evaluation at
-// one sample shared by corr_point and corr_bank_finish.
+// shared by corr_scan_s1 (corr.hip, one channel per launch), corr_bank_s1
+// (corr_bank.hip, one channel per grid row) and corr_all_map (corr_all.hip).
+// The scan stores no per-sample values: the registers after it are the tail's
+// (corr_tail.h).
 #pragma once
 #include <algorithm>
 
@@ -267,51 +268,6 @@ __device__ __forceinline__ void corr_scan_tile(const uint32_t *__restrict__ in, 
     if (1 < nrem && corr_hit(pc1, c_0, c_1, e_0)) hit = 1;
     if (0 < nrem && corr_hit(pc2, pc1, c_0, pe1)) hit = 0;
     if (hit >= 0) atomicMin(best, (unsigned)(i0 + lb + hit));
-}
-
-// The registers after a fused scan (the scan stores no per-sample values):
-// corr and energy at last-2 .. last, last = the detected sample (b) or
-// n - 1, each a direct sum over the N taps with corr_eval's arithmetic
-// (int32 wrap-around sums, so equal to the scan's sliding energy).  One block
-// of 256 lanes; out[k] = corr(last - k), out[3 + k] = energy(last - k) for
-// last - k >= 0.
-__device__ __forceinline__ void corr_point_regs(const uint32_t *__restrict__ in, long n,
-                                                const uint32_t *__restrict__ hist,
-                                                const int32_t *__restrict__ coef, unsigned N, unsigned S, unsigned cs,
-                                                unsigned b, uint32_t *__restrict__ out) {
-    __shared__ uint32_t red[3][3][256];
-    const long last = b != 0xffffffffu ? (long)b : n - 1;
-    const long NSm1 = (long)N * S - 1;
-    for (int k = 0; k < 3; ++k) {
-        uint32_t tr = 0, ti = 0, e = 0;
-        const long i = last - k;
-        if (i >= 0)
-            for (unsigned m = threadIdx.x; m < N; m += blockDim.x) {
-                const uint32_t w = corr_fetch(in, hist, i - (long)(N - 1 - m) * S, NSm1);
-                const int32_t hr = sext16(w), hi = sext16_hi(w);
-                const int32_t cr = coef[2 * m], ci = coef[2 * m + 1];
-                tr += (uint32_t)hr * (uint32_t)cr - (uint32_t)hi * (uint32_t)ci;
-                ti += (uint32_t)hr * (uint32_t)ci + (uint32_t)hi * (uint32_t)cr;
-                e += (uint32_t)hr * (uint32_t)hr + (uint32_t)hi * (uint32_t)hi;
-            }
-        red[k][0][threadIdx.x] = tr;
-        red[k][1][threadIdx.x] = ti;
-        red[k][2][threadIdx.x] = e;
-    }
-    __syncthreads();
-    for (int w = 128; w >= 1; w >>= 1) {
-        if ((int)threadIdx.x < w)
-            for (int k = 0; k < 3; ++k)
-                for (int q = 0; q < 3; ++q) red[k][q][threadIdx.x] += red[k][q][threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x < 3) {
-        const int k = threadIdx.x;
-        const int32_t sr = (int32_t)red[k][0][0] >> (cs & 31u), si = (int32_t)red[k][1][0] >> (cs & 31u);
-        const int32_t ar = sr >> 2, ai = si >> 2;
-        out[k] = (uint32_t)ar * (uint32_t)ar + (uint32_t)ai * (uint32_t)ai;
-        out[3 + k] = red[k][2][0] >> ((unsigned)((int)cs / 2) & 31u);
-    }
 }
 
 }  // namespace srcdsp

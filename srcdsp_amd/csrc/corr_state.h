@@ -1,6 +1,6 @@
-// corr_state.h -- the correlator handle and the geometry of its dot2 tiles,
-// shared between corr.hip (the single-channel calls) and corr_bank.hip
-// (srcdsp_corr_step_batched).
+// corr_state.h -- the correlator handle, its host staging and the geometry of
+// its dot2 tiles, shared by corr.hip (the single-channel calls), corr_bank.hip
+// (srcdsp_corr_step_batched) and corr_all.hip (srcdsp_corr_step_all).
 #pragma once
 #include <vector>
 
@@ -21,10 +21,11 @@ struct srcdsp_corr_state {
     uint32_t *d_hist[2] = {nullptr, nullptr};  // last NS-1 effective samples (packed ci16)
     int cur = 0;
     GrowBuf corr_vals{GrowBuf::kDevice}, en_vals{GrowBuf::kDevice};  // per-sample scratch of the segmented kernels
+    // the single-channel scans' `best` word
     unsigned *d_best = nullptr;
-    // scratch of the batched calls this handle led (hs[0] of
-    // srcdsp_corr_step_batched): per channel a best slot, a result row and a
-    // bitSamples row on the device, and their pinned host mirror
+    // the tail's results, device and pinned host mirror: a result row and a
+    // bitSamples row of this handle's own steps, or per channel of the batched
+    // calls it led (hs[0] of srcdsp_corr_step_batched / _all_batched)
     GrowBuf bank;
     // CorrState (correlators.h:59-81)
     uint32_t energy[3] = {0, 0, 0}, corr[3] = {0, 0, 0};
@@ -60,6 +61,16 @@ __host__ __device__ constexpr int corr_scan_lds_words(int NP) { return corr_lds_
 // the fused scan serves this handle (S == 1, int16-range pattern, NP taps stageable)
 inline bool corr_fused_shape(const srcdsp_corr_state &c) {
     return c.taps16 && c.NP <= kCorrDot2MaxTaps && c.S == 1;
+}
+
+// the *_host entry points: n host samples into the handle's pinned stage and
+// on to its device buffer (c.stage.d_buf), on the handle's own stream
+inline int corr_stage_in(srcdsp_corr_state &c, const void *in, size_t n) {
+    const int rc = c.stage.reserve(4 * n, 4 * n);
+    if (rc) return rc;
+    host_copy(c.stage.h_buf, in, 4 * n);
+    SRCDSP_HIP_TRY(hipMemcpyAsync(c.stage.d_buf, c.stage.h_buf, 4 * n, hipMemcpyHostToDevice, c.stage.stream));
+    return SRCDSP_OK;
 }
 
 }  // namespace srcdsp
