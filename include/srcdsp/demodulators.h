@@ -12,6 +12,10 @@
  * (assert, or std::runtime_error under NDEBUG): a first step() of no more
  * samples than the sync pattern has bits, a preamble longer than the
  * reference vector, a frequency word outside +-4096.
+ *
+ * dsptl::DemodulatorSdpsk<int16_t> is an extension with no reference class:
+ * the differential receiver of SymbolMapperSdpsk, one independent decision per
+ * sample; its bank is srcdsp_sdpsk_step_batched.
  */
 #ifndef SRCDSP_DROPIN_DEMODULATORS_H
 #define SRCDSP_DROPIN_DEMODULATORS_H
@@ -99,6 +103,53 @@ public:
 
 private:
     srcdsp_demod_t h_;
+};
+
+template <class InType>
+class DemodulatorSdpsk;
+
+/// Extension (no reference class): the receiver of SymbolMapperSdpsk
+/// (modulators.h:82-131).  bit[i] = Im(x[i] conj(x[i - D])) > 0, soft[i] =
+/// limitScale<int8_t, int32_t> of that product (dsp_complex.h:45-63), D the
+/// samples per symbol (1..64), the samples before the first step zero.
+template <>
+class DemodulatorSdpsk<int16_t> {
+public:
+    explicit DemodulatorSdpsk(unsigned D = 1, unsigned shift = 0) : h_(nullptr) {
+        srcdsp_detail::check(srcdsp_sdpsk_create(&h_, D, shift), "DemodulatorSdpsk");
+    }
+    ~DemodulatorSdpsk() { srcdsp_sdpsk_destroy(h_); }
+    /// copies: D, the shift and the carry
+    DemodulatorSdpsk(const DemodulatorSdpsk &o)
+        : h_(srcdsp_detail::clone_handle(o.h_, srcdsp_sdpsk_clone, "DemodulatorSdpsk(copy)")) {}
+    DemodulatorSdpsk(DemodulatorSdpsk &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    DemodulatorSdpsk &operator=(DemodulatorSdpsk o) noexcept {
+        std::swap(h_, o.h_);
+        return *this;
+    }
+
+    /// soft bits, one per sample; the vector is sized to in.size()
+    void step(const std::vector<std::complex<int16_t>> &in, std::vector<int8_t> &soft) {
+        soft.resize(in.size());
+        srcdsp_detail::check(srcdsp_sdpsk_step_host(h_, in.data(), in.size(), soft.data(), nullptr), "step");
+    }
+    /// hard bits (0 / 1), as SymbolMapperSdpsk::step takes them
+    void step(const std::vector<std::complex<int16_t>> &in, std::vector<uint8_t> &bits) {
+        bits.resize(in.size());
+        srcdsp_detail::check(srcdsp_sdpsk_step_host(h_, in.data(), in.size(), nullptr, bits.data()), "step(bits)");
+    }
+    /// device input, device outputs of in.size each; either span may be empty
+    void step(const DeviceSpan<const std::complex<int16_t>> &in, DeviceSpan<int8_t> soft, DeviceSpan<uint8_t> bits,
+              void *stream = nullptr) {
+        srcdsp_detail::check(srcdsp_sdpsk_step(h_, in.data, in.size, soft.data, bits.data, stream), "step(device)");
+    }
+    void reset() { srcdsp_detail::check(srcdsp_sdpsk_reset(h_), "reset"); }
+    void setShift(unsigned shift) { srcdsp_detail::check(srcdsp_sdpsk_set_shift(h_, shift), "setShift"); }
+    /// the C ABI handle, for srcdsp_sdpsk_step_batched
+    srcdsp_sdpsk_t handle() const { return h_; }
+
+private:
+    srcdsp_sdpsk_t h_;
 };
 
 }  // namespace dsptl

@@ -728,6 +728,78 @@ SRCDSP_API int srcdsp_demod_step_batched(const srcdsp_demod_t *hs, int channels,
                                          size_t *n_soft, int32_t *error, void *stream);
 
 /* ============================================================================
+ * The differential SDPSK demodulator: an extension with no reference class,
+ * the receiver of SymbolMapperSdpsk (modulators.h:82-131), which advances the
+ * phase by +90 degrees for a one and by -90 degrees for a zero.  A handle has
+ * a lag D (the samples per symbol), a soft shift and a carry of D samples.
+ * With v = carry ++ in[0..n), a = in[i] and b = v[i] (in[i-D], or carry[i] for
+ * i < D):
+ *   tq      = im(a)*re(b) - re(a)*im(b)      Im(a conj(b)), exact in int32
+ *   soft[i] = limitScale<int8_t, int32_t>(tq, shift)     (dsp_complex.h:45-63:
+ *             an arithmetic shift, then a clamp to [-128, 127])
+ *   bit[i]  = tq > 0 ? 1 : 0                 what srcdsp_mapper_step was fed
+ *   carry'  = v[n .. n+D)                    the last D samples, also for n < D
+ * The carry is zero after create and reset, so the first D outputs are soft 0
+ * and bit 0: start a burst's window D samples early and drop D outputs.  No
+ * PLL, no rotation and no frequency correction: a residual offset w tilts the
+ * decision by w*D out of a 90 degree margin.
+ * Every refusal below comes before any HIP call and changes no handle.
+ * ==========================================================================*/
+typedef struct srcdsp_sdpsk *srcdsp_sdpsk_t;
+/* Extension (modulators.h:82-131 received, dsp_complex.h:45-63): 1 <= D <= 64
+ * and shift 0..31 (SRCDSP_ERR_ARG otherwise), carry 0.  No device call: a
+ * handle is a host object until it steps on device buffers. */
+SRCDSP_API int srcdsp_sdpsk_create(srcdsp_sdpsk_t *out, unsigned D, unsigned shift);
+/* Extension (modulators.h:82-131, dsp_complex.h:45-63) */
+SRCDSP_API int srcdsp_sdpsk_destroy(srcdsp_sdpsk_t h);
+/* Extension (modulators.h:82-131, dsp_complex.h:45-63): a value copy, D, the
+ * shift and the carry (waits for the last step) */
+SRCDSP_API int srcdsp_sdpsk_clone(srcdsp_sdpsk_t h, srcdsp_sdpsk_t *out);
+/* Extension (modulators.h:82-131, dsp_complex.h:45-63): carry = 0, as a new
+ * handle; D and the shift stay */
+SRCDSP_API int srcdsp_sdpsk_reset(srcdsp_sdpsk_t h);
+/* Extension (the shift of dsp_complex.h:45-63 behind modulators.h:82-131):
+ * 0..31, SRCDSP_ERR_ARG otherwise; holds from the next step on */
+SRCDSP_API int srcdsp_sdpsk_set_shift(srcdsp_sdpsk_t h, unsigned shift);
+/* Extension (modulators.h:82-131, dsp_complex.h:45-63): D, the shift and the
+ * carry (D complex<int16_t>: 2*D int16_t, carry[i] is the next step's b for
+ * in[i]); waits for the handle's last step.  Null pointers are skipped. */
+SRCDSP_API int srcdsp_sdpsk_get_state(srcdsp_sdpsk_t h, unsigned *D, unsigned *shift, int16_t *carry);
+/* Extension (modulators.h:82-131, dsp_complex.h:45-63): the samples one
+ * workgroup of the kernel covers, the largest D, and the persistent workgroups
+ * of a launch: 0, the kernel is not persistent (one workgroup per tile and
+ * row).  No device call; null pointers are skipped. */
+SRCDSP_API int srcdsp_sdpsk_geometry(int *tile_samples, unsigned *max_lag, int *workgroups);
+/* Extension (modulators.h:82-131, dsp_complex.h:45-63): one step over n
+ * complex<int16_t> in device memory; n int8 to d_soft and n uint8 to d_bits.
+ * Either output may be NULL, not both (SRCDSP_ERR_ARG, as for a null d_in).
+ * Asynchronous on `stream`: nothing comes back to the host.  Successive steps
+ * of one handle are ordered across streams.  n == 0 changes nothing.  Offsets
+ * are 64-bit: no INT_MAX limit on n.  d_in at any sample offset; an output off
+ * a 4-byte boundary is stored byte by byte. */
+SRCDSP_API int srcdsp_sdpsk_step(srcdsp_sdpsk_t h, const void *d_in, size_t n, int8_t *d_soft, uint8_t *d_bits,
+                                 void *stream);
+/* Extension (modulators.h:82-131, dsp_complex.h:45-63): the same on host
+ * buffers, with the kernel's own arithmetic on the host.  No HIP call for a
+ * handle that has not stepped on device buffers; one whose carry the device
+ * holds takes it back first (waits for its last step). */
+SRCDSP_API int srcdsp_sdpsk_step_host(srcdsp_sdpsk_t h, const void *in, size_t n, int8_t *soft, uint8_t *bits);
+/* Extension (modulators.h:82-131, dsp_complex.h:45-63).  C demodulators in one
+ * call: row c is exactly srcdsp_sdpsk_step(hs[c], d_in + c*in_stride +
+ * (in_offset ? in_offset[c] : 0) samples, n, d_soft + c*soft_stride, d_bits +
+ * c*bits_stride, stream).  in_offset is a host array of `channels` entries or
+ * NULL.  in_stride == 0: every row lies in one buffer (all the hits of one
+ * stream).  The handles share D and the shift (their carries may differ) and
+ * every handle is listed once (SRCDSP_ERR_ARG otherwise); channels >= 1, no
+ * upper limit (65535 rows per launch).  The stride of an output that is not
+ * NULL is >= n (SRCDSP_ERR_SIZE otherwise).  The row table of a call lives on
+ * hs[0], in a ring of 4: a bank call waits on the host for the fourth call
+ * before it that the same handle led, if that one is still running. */
+SRCDSP_API int srcdsp_sdpsk_step_batched(const srcdsp_sdpsk_t *hs, int channels, const void *d_in, size_t in_stride,
+                                         const size_t *in_offset, size_t n, int8_t *d_soft, size_t soft_stride,
+                                         uint8_t *d_bits, size_t bits_stride, void *stream);
+
+/* ============================================================================
  * estimateFreq<int16_t, L>   (dsptl_miscellaneous.h:43-58)
  * The frequency of n complex<int16_t> samples in rad/sample from the lag-L
  * autocorrelation sum x[i] * conj(x[i+L]), i < n - L (for e^{+jwn} it returns

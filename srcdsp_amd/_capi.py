@@ -141,6 +141,16 @@ SIGNATURES = {
     "srcdsp_demod_step_host": (I, [VP, VP, SZ, VP, SZ, C.POINTER(C.c_size_t), I32P]),
     "srcdsp_demod_step_batched": (I, [HP, I, VP, SZ, C.POINTER(C.c_size_t), SZ, VP, SZ, C.POINTER(C.c_size_t), I32P,
                                       VP]),
+    "srcdsp_sdpsk_create": (I, [HP, U, U]),
+    "srcdsp_sdpsk_destroy": (I, [VP]),
+    "srcdsp_sdpsk_clone": (I, [VP, HP]),
+    "srcdsp_sdpsk_reset": (I, [VP]),
+    "srcdsp_sdpsk_set_shift": (I, [VP, U]),
+    "srcdsp_sdpsk_get_state": (I, [VP, UP, UP, I16P]),
+    "srcdsp_sdpsk_geometry": (I, [IP, UP, IP]),
+    "srcdsp_sdpsk_step": (I, [VP, VP, SZ, VP, VP, VP]),
+    "srcdsp_sdpsk_step_host": (I, [VP, VP, SZ, VP, VP]),
+    "srcdsp_sdpsk_step_batched": (I, [HP, I, VP, SZ, C.POINTER(C.c_size_t), SZ, VP, SZ, VP, SZ, VP]),
     "srcdsp_freqest_create": (I, [HP, I]),
     "srcdsp_freqest_destroy": (I, [VP]),
     "srcdsp_freqest_geometry": (I, [VP, IP, IP, IP, IP]),

@@ -1230,6 +1230,97 @@ def demod_step_batched(demods, x, offsets=None, n=None):
     return soft[:, :n], list(ns), list(err)
 
 
+# ============================================================== DemodulatorSdpsk
+class DemodulatorSdpsk(_Handle):
+    """The receiver of SymbolMapperSdpsk (no reference class): bit = sign of
+    Im(x[i] * conj(x[i - D])), D samples per symbol (1..64); the soft bit is
+    that product shifted right by ``shift`` (0..31) and clamped to int8.  No
+    PLL: every output is independent.  The first D outputs after a reset read
+    the zero carry and are 0."""
+
+    _destroy = "srcdsp_sdpsk_destroy"
+    _clone = "srcdsp_sdpsk_clone"
+
+    def __init__(self, D: int = 1, shift: int = 0):
+        self._h = C.c_void_p()
+        A.call("srcdsp_sdpsk_create", C.byref(self._h), int(D), int(shift))
+        self.D = int(D)
+
+    def reset(self):
+        A.call("srcdsp_sdpsk_reset", self._h)
+
+    def setShift(self, shift: int):
+        A.call("srcdsp_sdpsk_set_shift", self._h, int(shift))
+
+    set_shift = setShift
+
+    def state(self):
+        """(D, shift, carry int16 [D, 2]): the carry is the last D samples seen."""
+        d, s = C.c_uint(), C.c_uint()
+        carry = np.zeros((self.D, 2), np.int16)
+        A.call("srcdsp_sdpsk_get_state", self._h, C.byref(d), C.byref(s), carry.ctypes.data_as(A.I16P))
+        return d.value, s.value, carry
+
+    def step(self, inp):
+        """Returns (soft int8 [n], bits uint8 [n]): device tensors for a device
+        input (asynchronous on torch's current stream), numpy arrays for a host
+        one."""
+        n = _nsamples(inp, "ci16")
+        if _is_device(inp):
+            import torch
+            soft = torch.empty(n, dtype=torch.int8, device=inp.device)
+            bits = torch.empty(n, dtype=torch.uint8, device=inp.device)
+            A.call("srcdsp_sdpsk_step", self._h, _ptr(inp), n, _ptr(soft), _ptr(bits), _stream(inp))
+        else:
+            x = _host(inp, "ci16")
+            soft, bits = np.zeros(n, np.int8), np.zeros(n, np.uint8)
+            A.call("srcdsp_sdpsk_step_host", self._h, _ptr(x), n, _ptr(soft), _ptr(bits))
+        return soft, bits
+
+
+def sdpsk_geometry():
+    """(tile_samples, max_lag, workgroups) of the SDPSK demodulator's kernel;
+    workgroups is 0: the kernel is not persistent."""
+    t, d, w = C.c_int(), C.c_uint(), C.c_int()
+    A.call("srcdsp_sdpsk_geometry", C.byref(t), C.byref(d), C.byref(w))
+    return t.value, d.value, w.value
+
+
+def sdpsk_step_batched(demods, x, offsets=None, n=None):
+    """Step C SDPSK demodulators of one D and shift in one call: row c is
+    exactly ``demods[c].step(x_c)``.  ``x`` is a device tensor of
+    complex<int16_t> samples: int16 [C, m, 2], one row per channel, or [m, 2],
+    one buffer every channel reads (all the hits of one stream).  ``offsets[c]``
+    (samples) moves channel c's first sample within its row; every channel
+    steps ``n`` samples (default: what the largest offset leaves of a row).
+    Returns (soft int8 [C, n], bits uint8 [C, n]) device tensors."""
+    import torch
+    ch = len(demods)
+    if ch < 1:
+        raise ValueError("sdpsk_step_batched: at least one demodulator")
+    if not _is_device(x):
+        raise TypeError("sdpsk_step_batched() takes a device-resident buffer")
+    if x.dim() not in (2, 3) or x.shape[-1] != 2 or x.element_size() != 2:
+        raise ValueError("sdpsk_step_batched: x is int16 [m, 2] (shared) or [C, m, 2]")
+    shared = x.dim() == 2
+    if not shared and x.shape[0] != ch:
+        raise ValueError("sdpsk_step_batched: one input row per demodulator")
+    m = x.shape[-2]
+    offs = [0] * ch if offsets is None else [int(o) for o in offsets]
+    if len(offs) != ch or min(offs) < 0 or max(offs) > m:
+        raise ValueError("sdpsk_step_batched: one offset per channel, within the row")
+    if n is None:
+        n = m - max(offs)
+    if n < 0 or max(offs) + n > m:
+        raise ValueError("sdpsk_step_batched: offset + n runs past the row")
+    stride = (max(n, 1) + 3) & ~3  # rows on 4-byte boundaries: whole-word stores
+    soft = torch.empty((ch, stride), dtype=torch.int8, device=x.device)
+    bits = torch.empty((ch, stride), dtype=torch.uint8, device=x.device)
+    A.call("srcdsp_sdpsk_step_batched", _handles(demods), ch, _ptr(x), 0 if shared else m, (C.c_size_t * ch)(*offs), n,
+           _ptr(soft), stride, _ptr(bits), stride, _stream(x))
+    return soft[:, :n], bits[:, :n]
+
+
 # ================================================================== estimateFreq
 class FreqEstimator(_Handle):
     """estimateFreq<int16_t, L> (dsptl_miscellaneous.h:43-58): the frequency of
